@@ -30,8 +30,24 @@ vs_baseline_note, per_model.
 Multi-GPU: one process per GPU, ``torch.distributed`` backend ``nccl`` (= RCCL over xGMI).
 
     python bench.py --gpus 1 --steps 1 --warmup 1
+    python bench.py --gpus 1 --full               # + the untimed anytime budget pass (--budget-pass)
     python bench.py --gpus 8                      # self-launches 8 ranks (no torchrun needed)
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8 --steps 1 --warmup 1
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the line.  ``--full`` adds what
+the headline figure does not need: the untimed budget pass (``pct_verified_at_budget``,
+``pct_verified_at_budget_sound``, ``budget_pass``).
+
+``--dump-outputs DIR`` writes what the LAST timed step computed, one ``DIR/<name>.npy`` per
+column of the per-partition records ``verify_chunk`` returns (all models concatenated, rows sorted
+by model then grid id; wall-time columns left out): ``model`` (index into the model list),
+``grid_id``, ``verdict`` (0 unknown, 1 sat, 2 unsat), ``stage`` (index into engine/stages.py
+STAGES), the counters ``h_attempt h_success b_cnt s_cnt st_cnt h_cnt t_cnt agree tp fp nodes
+c_check v_accurate``, ``stage_nodes`` [n, 5] and the counterexample pairs ``cex_x`` / ``cex_xp``
+[n, inputs] (zero where the verdict is not SAT).  float32, except ``nodes`` / ``stage_nodes`` in
+float64; with N > 1 ranks each rank writes its own rows as ``<name>.rank<r>.npy``.  Inputs
+(weights, partition order, simulation points) depend on the arguments only, so two builds run
+with the same arguments can be compared array for array.
 
 Self-launch: with ``--gpus N > 1`` and no ``WORLD_SIZE`` in the environment, this process
 starts N child processes of itself (rank env vars set, rendezvous on 127.0.0.1) BEFORE any GPU
@@ -111,9 +127,14 @@ def parse_args(argv=None):
     ap.add_argument("--lp-budget", type=int, default=4096,
                     help="with --smt milp/auto: verified-LP branch-and-bound nodes per partition (stage 'lp', "
                          "sound UNSAT); 0 = the HiGHS MILP")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the untimed budget pass "
+                         "(--budget-pass); off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the per-partition records of the last timed step as DIR/<name>.npy")
     ap.add_argument("--budget-pass", type=float, default=10.0,
-                    help="after the timed steps, one untimed pass over the same grid in anytime mode with this "
-                         "many seconds per model (growing BaB budgets + falsifier + MILP rounds on the residue): "
+                    help="with --full: after the timed steps, one untimed pass over the same grid in anytime mode "
+                         "with this many seconds per model (growing BaB budgets + falsifier + MILP rounds on the residue): "
                          "reports pct_verified_at_budget (0 = skip; default 10 s per model adds ~16 s)")
     ap.add_argument("--no-heuristic", action="store_true",
                     help="skip the reference's unsound heuristic retry (sound verdicts only)")
@@ -182,6 +203,33 @@ def _mem_delta(a, b):
             "dev_cache_hits": b["dev_hits"] - a["dev_hits"], "host_mallocs": b["host_mallocs"] - a["host_mallocs"],
             "dev_gb": round((b["dev_live_bytes"] + b["dev_cached_bytes"]) / 2 ** 30, 3),
             "host_pinned_gb": round((b.get("host_live_bytes", 0) + b.get("host_cached_bytes", 0)) / 2 ** 30, 3)}
+
+
+DUMP_COUNTERS = ("h_attempt", "h_success", "b_cnt", "s_cnt", "st_cnt", "h_cnt", "t_cnt", "agree", "tp", "fp",
+                 "c_check", "v_accurate")
+
+
+def dump_outputs(out_dir: str, parts, rank: int, world: int) -> None:
+    """``parts``: [(model index, core columns of one work item)] of the last timed step."""
+    from fairify_amd.engine.stages import code as stage_code
+
+    os.makedirs(out_dir, exist_ok=True)
+    model = np.concatenate([np.full(len(c["grid_id"]), k, dtype=np.int64) for k, c in parts])
+    cat = lambda name: np.concatenate([np.asarray(c[name]) for _, c in parts])
+    gid, verdict = cat("grid_id"), cat("verdict")
+    o = np.lexsort((gid, model))
+    sat = (verdict == "sat")[o]
+    cols = {"model": model[o].astype(np.float32), "grid_id": gid[o].astype(np.float32),
+            "verdict": np.select([verdict == "sat", verdict == "unsat"], [1, 2], 0)[o].astype(np.float32),
+            "stage": np.array([stage_code(x) for x in cat("stage")], dtype=np.float32)[o],
+            "nodes": cat("nodes")[o].astype(np.float64), "stage_nodes": cat("stage_nodes")[o].astype(np.float64)}
+    for name in DUMP_COUNTERS:
+        cols[name] = cat(name)[o].astype(np.float32)
+    for name in ("cex_x", "cex_xp"):
+        cols[name] = np.where(sat[:, None], cat(name)[o], 0).astype(np.float32)
+    sfx = f".rank{rank}" if world > 1 else ""
+    for name, a in cols.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
 
 
 def main() -> None:
@@ -382,6 +430,7 @@ def main() -> None:
 
     NPM = 3 + len(STAGE_NODE_COLS)
     pm_tot = np.zeros((len(models), NPM))
+    dump_parts = []       # --dump-outputs: (model, core columns) of every item of the current step
 
     def one_item(k: int, j, ids: np.ndarray, uis=None, high: bool = False):
         m, be = models[k], backends[k]
@@ -391,6 +440,8 @@ def main() -> None:
             if info.device.type == "cuda":
                 torch.cuda.current_stream(info.device).synchronize()
         item_cost[(k, j)] = time.time() - t_item
+        if args.dump_outputs:
+            dump_parts.append((k, recs.core))
         if ITEM_LOG:
             print(f"[item] step {step_no[0]} {models[k].name} chunk {j} n={len(ids)} start "
                   f"{t_item - step_t0[0]:.3f}s took {item_cost[(k, j)]:.3f}s", file=sys.stderr, flush=True)
@@ -419,6 +470,7 @@ def main() -> None:
 
     def run_step(step: int, timed: bool = False):
         step_no[0], step_t0[0] = step, time.time()
+        del dump_parts[:]
         items = items_for_step(step)
         items.sort(key=lambda it: (-item_cost.get((it[0], it[1]), 0.0), -models[it[0]].n_neurons))
         res = []
@@ -551,7 +603,9 @@ def main() -> None:
                                "nodes": {c: int(round(pm_all[k, 3 + i])) for i, c in enumerate(STAGE_NODE_COLS)}}
                       for k, m in enumerate(models)},
     }
-    if args.budget_pass > 0:
+    if args.dump_outputs and args.steps > 0 and dump_parts:
+        dump_outputs(args.dump_outputs, dump_parts, info.rank, info.world)
+    if args.full and args.budget_pass > 0:
         # per-model wall budget B: every (model, chunk) item gets the chunk's share of B for its
         # anytime phase; items of all models run concurrently on the host streams, so the pass
         # takes about B plus the fixed-schedule time of one step

@@ -3,7 +3,7 @@
 # the residue), and the beta fixed pass inside the timed step at budgets 64 / 128
 set -o pipefail
 OUT=gpurun_out/r6m; mkdir -p $OUT
-timeout -k 10 400 python -u bench.py --steps 3 --warmup 1 > $OUT/def.json 2> $OUT/def.err || { tail -20 $OUT/def.err; exit 1; }
+timeout -k 10 400 python -u bench.py --steps 3 --warmup 1 --full > $OUT/def.json 2> $OUT/def.err || { tail -20 $OUT/def.err; exit 1; }
 python - $OUT/def.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -104,17 +104,14 @@ def test_analyze_writes_hybrid_and_case_csvs(tmp_path):
     assert counts["Case 3"] == res["cases"]["sat_fairer"]
 
 
-def test_ac3_group_metrics_pinned_to_reference_log():
+def test_ac3_group_metrics_pinned_to_reference_log(adult_data):
     """AC-3 on the Adult test split vs the fork's logged AIF360 values (AC-3.ipynb:752-762 at 3 dp,
     and the 4-dp "Original CNT: 0.8890" of :2086, reproduced by AIF360's ball-tree kNN)."""
     from fairify_amd.analysis.metrics import all_metrics, consistency
     from fairify_amd.data import tabular
     from fairify_amd.models.zoo import get_model
 
-    try:
-        ds = tabular.load("adult", allow_synthetic=False)
-    except Exception:
-        pytest.skip("Adult data absent (parity unpinned)")
+    ds = tabular.load("adult", allow_synthetic=False)
     m = get_model("AC-3", weights="zoo")
     yp = m.predict(ds.X_test)
     r = all_metrics(ds.X_test, ds.y_test, yp, 8)

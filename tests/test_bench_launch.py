@@ -113,6 +113,46 @@ def test_sound_fields_exclude_heuristic_and_milp():
     assert d3["unsat_sound"] == d3["unsat"] - us3["heuristic"]
 
 
+def test_budget_pass_only_with_full():
+    """A plain run stops after the timed steps; the untimed budget pass and its fields need --full."""
+    small = ("--models", "AC-8", "--limit", "16", "--budget-pass", "0.5")
+    plain = _bench(1, small)
+    assert not {"budget_pass", "pct_verified_at_budget", "pct_verified_at_budget_sound"} & set(plain)
+    full = _bench(1, small + ("--full",))
+    assert full["budget_pass"]["attempted"] == 16 and full["budget_pass"]["seconds_per_model"] == 0.5
+    assert 0.0 <= full["pct_verified_at_budget_sound"] <= full["pct_verified_at_budget"] <= 100.0
+    for k in ("sat", "unsat", "unknown", "sat_by_stage", "unsat_by_stage", "steps", "warmup"):
+        assert full[k] == plain[k], k
+
+
+def test_dump_outputs_last_step_records(tmp_path):
+    """--dump-outputs: one .npy per record column of the last timed step, float32 / float64, rows by
+    (model, grid id), consistent with the JSON totals and identical from run to run."""
+    import numpy as np
+
+    runs = []
+    for name, steps in (("a", "1"), ("b", "2")):
+        d = _bench(1, ("--dump-outputs", str(tmp_path / name), "--steps", steps, "--limit", "16"))
+        assert d["steps"] == int(steps)
+        runs.append((d, {f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))}))
+    (da, a), (db, b) = runs
+    assert set(a) == set(b) >= {"model", "grid_id", "verdict", "stage", "nodes", "stage_nodes", "agree", "cex_x",
+                                "cex_xp"}
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and len(a[k]) == 32, k
+        assert np.array_equal(a[k], b[k]), k          # the last step only, whatever --steps is
+    assert a["cex_x"].shape == (32, 13) and a["stage_nodes"].shape == (32, 5)
+    assert a["model"].tolist() == [0.0] * 16 + [1.0] * 16
+    assert all((np.diff(a["grid_id"][a["model"] == m]) > 0).all() for m in (0, 1))
+    assert ((a["verdict"] == 1).sum(), (a["verdict"] == 2).sum(), (a["verdict"] == 0).sum()) == \
+        (da["sat"], da["unsat"], da["unknown"])
+    assert 2 * da["sat"] == db["sat"]                  # the JSON totals cover every timed step
+    sat = a["verdict"] == 1
+    assert (a["cex_x"][~sat] == 0).all() and (a["cex_x"][sat] != a["cex_xp"][sat]).any(axis=1).all()
+    for i, col in enumerate(("bab", "relu", "beta", "anytime", "heuristic")):
+        assert a["stage_nodes"][:, i].sum() == sum(m["nodes"][col] for m in da["per_model"].values()), col
+
+
 def test_emulated_lpt_shards_cover_the_grid():
     """--emulate-shard r/N with the LPT balancer: the warmup step measures every unit, the timed
     step runs rank r's units; the N emulated shards partition the grid (attempted and decided

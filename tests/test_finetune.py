@@ -1,26 +1,21 @@
 """GC/BM fine-tune on synthetic data with early stopping (src/GC/new_model.py:8-58) on the
-reference's own synthetic GC CSV when present, else on rows of the synthetic domain."""
+reference's own synthetic GC CSV (stored under tests/golden/experimentData)."""
 import os
 
 import numpy as np
 import pandas as pd
-import pytest
 
 from fairify_amd.models.zoo import get_model
-from fairify_amd.repair.finetune import SUITE_SPECS, encode_synthetic, finetune, finetune_csv
+from fairify_amd.repair.finetune import SUITE_SPECS, encode_synthetic, finetune_csv
 
-REF_CSV = "/root/reference/experimentData/task2/TabFPN/GC2/2000-100/synthetic-german-predicted-gpt2.csv"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+# experimentData/task2/TabFPN/GC2/2000-100/synthetic-german-predicted-gpt2.csv of the reference
+REF_CSV = os.path.join(GOLDEN, "experimentData", "synthetic-german-predicted-gpt2.csv")
 
 
 def test_finetune_early_stopping_restores_best():
     m = get_model("GC-2", weights="zoo")
-    if os.path.exists(REF_CSV):
-        r = finetune_csv(m, REF_CSV, "german", epochs=30, seed=0)
-    else:   # parity unpinned: synthetic rows labelled by the model itself
-        from fairify_amd.data import tabular
-
-        ds = tabular.synthetic(tabular.DOMAINS["german"], n=600, seed=1, mlp=m)
-        r = finetune(m, ds.X_train, ds.y_train, epochs=30, seed=0)
+    r = finetune_csv(m, REF_CSV, "german", epochs=30, seed=0)
     assert r.train_rows > 0 and r.val_rows > 0
     assert r.best_epoch == int(np.argmin(r.val_loss)) + 1          # restore_best_weights
     stopped = r.epochs_run < 30
@@ -36,20 +31,15 @@ def test_encode_synthetic_fresh_label_encoders():
     assert X[:, 0].tolist() == [0, 1, 0] and X[:, 1].tolist() == [6, 12, 24] and y.tolist() == [1, 0, 1]
 
 
-REF_CE = "/root/reference/experimentData/task5/AC/counterexamples-AC-3.csv"
+# experimentData/task5/AC/counterexamples-AC-3.csv of the reference, gzipped
+REF_CE = os.path.join(GOLDEN, "experimentData", "counterexamples-AC-3.csv.gz")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CE), reason="reference counterexample CSV absent (parity unpinned)")
-def test_reencode_decoded_counterexamples_ac3():
+def test_reencode_decoded_counterexamples_ac3(adult_data):
     """src/AC/detect_bias.py:140-167 on the fork's own decoded AC-3 counterexamples: rows come
     back in the model's feature order, consecutive rows differ only in sex, labels kept."""
-    from fairify_amd.data import tabular
     from fairify_amd.repair.retrain import load_pairs
 
-    try:
-        tabular.load("adult", allow_synthetic=False)
-    except Exception:
-        pytest.skip("Adult data absent")
     X, y = load_pairs(REF_CE, 13, 8, suite="adult")
     assert X.shape[1] == 13 and len(X) % 2 == 0 and len(X) > 1000
     assert y is not None and set(np.unique(y)) <= {0, 1}

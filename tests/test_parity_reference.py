@@ -4,20 +4,14 @@ GC-3 / GC-4 decided all 201 partitions in the paper, so their exact SAT/UNSAT sp
 model-level oracle: (age) GC3 195 SAT / 6 UNSAT, GC4 2 SAT / 199 UNSAT; identical for sex.
 AC-3's test accuracy 0.8452 is printed in experimentData/task5/results/AC/AC-3.ipynb:2082-2084.
 """
-import os
-
-import numpy as np
 import pytest
 
 from fairify_amd import presets
 from fairify_amd.engine.pipeline import VerifyConfig
 from fairify_amd.engine.runner import model_accuracy, run_preset
-from fairify_amd.models.zoo import get_model, has_weights
-
-DATA = os.path.isdir(os.environ.get("FAIRIFY_DATA", "/root/reference/data"))
+from fairify_amd.models.zoo import get_model
 
 
-@pytest.mark.skipif(not has_weights("GC-3"), reason="zoo weights not shipped")
 @pytest.mark.parametrize("preset", ["src/GC-age", "src/GC-sex"])
 @pytest.mark.parametrize("model,sat,unsat", [("GC-3", 195, 6), ("GC-4", 2, 199)])
 def test_table_v_gc_exact_counts(tmp_path, preset, model, sat, unsat):
@@ -27,7 +21,6 @@ def test_table_v_gc_exact_counts(tmp_path, preset, model, sat, unsat):
     assert (r["SAT"], r["UNSAT"], r["UNK"]) == (sat, unsat, 0)
 
 
-@pytest.mark.skipif(not (DATA and has_weights("AC-3")), reason="adult data / weights missing")
-def test_ac3_test_accuracy_matches_reference_log():
+def test_ac3_test_accuracy_matches_reference_log(adult_data):
     acc = model_accuracy(get_model("AC-3"), "adult")
     assert abs(acc - 0.8452) < 5e-5
