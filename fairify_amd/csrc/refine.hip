@@ -527,6 +527,7 @@ RefineKernel select_refine_shaped(const NetDesc& net, int TM, bool wg) {
       shaped_refine<4, 16, 64, 32, 16, 8, 4, 1>(),    // BM-8
       shaped_refine<4, 13, 64, 64, 1>(),              // AC-5
       shaped_refine<7, 13, 100, 100, 1>(),            // AC-4
+      shaped_refine<1, 13, 10, 10, 10, 10, 1>(),      // AC-11
   };
   const int tmb = TM <= 1 ? 1 : TM <= 2 ? 2 : TM <= 4 ? 4 : TM <= 7 ? 7 : 10;
   for (const auto& s : v) {
@@ -665,4 +666,5 @@ FA_LDS_REGISTER(FA_LDS_K(fa_refine_kernel<1>), FA_LDS_K(fa_refine_kernel<2>), FA
 FA_LDS_REGISTER(FA_LDS_K((fa_refine_kernel<4, false, FaShape<13, 64, 32, 16, 8, 4, 1>>)),
                 FA_LDS_K((fa_refine_kernel<4, false, FaShape<16, 64, 32, 16, 8, 4, 1>>)),
                 FA_LDS_K((fa_refine_kernel<4, false, FaShape<13, 64, 64, 1>>)),
-                FA_LDS_K((fa_refine_kernel<7, false, FaShape<13, 100, 100, 1>>)));
+                FA_LDS_K((fa_refine_kernel<7, false, FaShape<13, 100, 100, 1>>)),
+                FA_LDS_K((fa_refine_kernel<1, false, FaShape<13, 10, 10, 10, 10, 1>>)));

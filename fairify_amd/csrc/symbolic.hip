@@ -355,7 +355,7 @@ __device__ __forceinline__ void fa_sym_layer(const NetDesc& net, const BoundArgs
   const float gnext = last ? 0.f : net.g_gemm[l + 1];
   const int noff = net.neuron_off[l];
   const int nc = cfg.nc;
-  const int n0 = net.dims[0];
+  const int n0 = CS ? S::dim(0) : net.dims[0];
   // neuron lane role in the epilogue: lanes 0-15 = U block, 16-31 = L block of neuron (lane & 15)
   const bool nl_act = lane < 32;
   const int ob = (lane >> 4) & 1;
@@ -365,7 +365,7 @@ __device__ __forceinline__ void fa_sym_layer(const NetDesc& net, const BoundArgs
     // (W_0 placed at output rows g * 16 / PG ..), K = the box's own input dims
     const float* boxtab = bxv + 2 * PG * SymSlab<NT, PG>::BOX;   // [2 PG][lo 16 | hi 16]
     const float g0 = net.g_gemm[0];
-    const int n0v = net.dims[0];
+    const int n0v = n0;
     f32x4 U[2][NT], Lq[2][NT];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -830,37 +830,48 @@ int tm_bucket(int NT, int TM) {
 }
 
 // Compile-time shapes (SymShape): the zoo's dominant layer chains, each instantiated for the (NT, TM
-// bucket) kernel the run-time selection picks for it, so launch geometry, LDS layout and arithmetic
+// bucket, paired / packed) kernel the run-time selection picks for it, so launch geometry, LDS layout and arithmetic
 // are the generic kernel's.  FAIRIFY_SYM_SHAPED=0 (read per launch: the bitwise-equality test
 // toggles it) keeps the run-time-shape kernels.
 struct ShapedKernel {
   int nt, tm;
+  bool pair;   // two box rows per wave (single-tile networks)
+  int pg;      // packed: boxes per MFMA tile (1: not packed)
   std::vector<int> dims;
   SymKernel k;
 };
-template <int NT, int TM, int... D>
+template <int NT, int TM, bool PAIR, int PG, int... D>
 ShapedKernel shaped() {
-  return {NT, TM, {D...}, fa_sym_kernel<NT, TM, false, 1, SymShape<D...>>};
+  return {NT, TM, PAIR, PG, {D...}, fa_sym_kernel<NT, TM, PAIR, PG, SymShape<D...>>};
 }
 
 const std::vector<ShapedKernel>& shaped_kernels() {
   static const std::vector<ShapedKernel> v = {
-      shaped<1, 4, 13, 64, 32, 16, 8, 4, 1>(),   // AC-7, PA folded (node-row expansion)
-      shaped<2, 4, 13, 64, 32, 16, 8, 4, 1>(),   // AC-7, no dim folded (beta tightening rows)
-      shaped<2, 4, 16, 64, 32, 16, 8, 4, 1>(),   // BM-8
-      shaped<1, 4, 13, 64, 64, 1>(),             // AC-5
-      shaped<1, 4, 13, 50, 1>(),                 // AC-3
-      shaped<1, 7, 13, 100, 100, 1>(),           // AC-4
-      shaped<1, 7, 13, 100, 1>(),                // AC-2
+      shaped<1, 4, false, 1, 13, 64, 32, 16, 8, 4, 1>(),   // AC-7, PA folded (node-row expansion)
+      shaped<2, 4, false, 1, 13, 64, 32, 16, 8, 4, 1>(),   // AC-7, no dim folded (beta tightening rows)
+      shaped<2, 4, false, 1, 16, 64, 32, 16, 8, 4, 1>(),   // BM-8
+      shaped<1, 4, false, 1, 13, 64, 64, 1>(),             // AC-5
+      shaped<1, 4, false, 1, 13, 50, 1>(),                 // AC-3
+      shaped<1, 7, false, 1, 13, 100, 100, 1>(),           // AC-4
+      shaped<1, 7, false, 1, 13, 100, 1>(),                // AC-2
+      // narrow single-tile chains, PA folded (NT = 1): paired (two box rows per wave) ...
+      shaped<1, 1, true, 1, 13, 16, 8, 1>(),               // AC-1
+      shaped<1, 1, true, 1, 13, 12, 12, 1>(),              // AC-6
+      shaped<1, 1, true, 1, 13, 10, 10, 10, 10, 1>(),      // AC-11
+      // ... and packed, two boxes per MFMA tile
+      shaped<1, 1, true, 2, 13, 5, 5, 1>(),                            // AC-8
+      shaped<1, 1, true, 2, 13, 5, 5, 5, 5, 1>(),                      // AC-10
+      // (AC-12's ten unrolled layers spill: 24 VGPRs, 100 B/lane of scratch against 0 for the
+      // run-time-shape kernel -- it keeps the latter)
   };
   return v;
 }
 
-SymKernel select_shaped(const NetDesc& net, int NT, int tmb) {
+SymKernel select_shaped(const NetDesc& net, int NT, int tmb, bool pair, int pg) {
   const char* e = getenv("FAIRIFY_SYM_SHAPED");
   if (e && *e == '0') return nullptr;
   for (const auto& s : shaped_kernels()) {
-    if (s.nt != NT || s.tm != tmb || (int)s.dims.size() != net.n_layers + 1) continue;
+    if (s.nt != NT || s.tm != tmb || s.pair != pair || s.pg != pg || (int)s.dims.size() != net.n_layers + 1) continue;
     bool same = true;
     for (int l = 0; l <= net.n_layers && same; ++l) same = s.dims[l] == net.dims[l];
     if (same) return s.k;
@@ -912,10 +923,8 @@ extern "C" int fa_sym_try_launch(const NetDesc& net, BoundArgs a, unsigned long 
   const int pg = (pair0 && net.pack_g > 1 && net.dims[0] <= 16 && use_pack()) ? net.pack_g : 1;
   if (pg > 1) k = select_packed(pg);
   if (!k) return 0;
-  if (!pair0) {   // a compile-time-shape instance of the same (NT, TM) kernel, when there is one
-    const SymKernel ks = select_shaped(net, NT, tmb);
-    if (ks) k = ks;
-  }
+  // a compile-time-shape instance of the same (NT, TM, paired / packed) kernel, when there is one
+  if (const SymKernel ks = select_shaped(net, NT, tmb, pair0, pg)) k = ks;
   int off = 0;
   if (pg > 1) {
     cfg.w_lds[0] = 0;
@@ -995,3 +1004,8 @@ FA_LDS_REGISTER(FA_LDS_K((fa_sym_kernel<1, 4, false, 1, SymShape<13, 64, 32, 16,
                 FA_LDS_K((fa_sym_kernel<1, 4, false, 1, SymShape<13, 50, 1>>)),
                 FA_LDS_K((fa_sym_kernel<1, 7, false, 1, SymShape<13, 100, 100, 1>>)),
                 FA_LDS_K((fa_sym_kernel<1, 7, false, 1, SymShape<13, 100, 1>>)));
+FA_LDS_REGISTER(FA_LDS_K((fa_sym_kernel<1, 1, true, 1, SymShape<13, 16, 8, 1>>)),
+                FA_LDS_K((fa_sym_kernel<1, 1, true, 1, SymShape<13, 12, 12, 1>>)),
+                FA_LDS_K((fa_sym_kernel<1, 1, true, 1, SymShape<13, 10, 10, 10, 10, 1>>)),
+                FA_LDS_K((fa_sym_kernel<1, 1, true, 2, SymShape<13, 5, 5, 1>>)),
+                FA_LDS_K((fa_sym_kernel<1, 1, true, 2, SymShape<13, 5, 5, 5, 5, 1>>)));
