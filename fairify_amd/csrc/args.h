@@ -444,6 +444,11 @@ struct BetaArgs {
                             // Lagrangian of the phase constraints alone (objective weight 0, multipliers
                             // in [0, 1]) is optimised; a rigorous value > 0 proves the region empty (bound
                             // := +inf); nothing else is written (scratch must hold [R, 16, NH])
+  // two-phase level (csrc/beta_opt16.hip): the batched optimiser's primal sums.  Both non-null: the
+  // primal-gap sums start from pgsum [R, 4, NH] (zA, zB, hA, hB) and the weight sum from pgn [R]
+  // instead of zero (iters = 0: the primal-gap rule sees the optimiser's averages); null: unused
+  const float* pgsum;
+  const float* pgn;
 };
 
 // Native beta-CROWN BaB level (csrc/beta_runtime.cpp, kernels csrc/beta_bab.hip): a device-resident

@@ -19,8 +19,10 @@
 // transposed copy too when it fits), the per-node bounds / records live in a per-wave LDS slab,
 // the optimiser state (current parameters, Adam moments) in a global scratch row per node that
 // stays L2-resident while the wave runs.  The network is a handful of KB and every node runs
-// ~100 dependent passes through it, so the kernel is latency / issue bound: MFMA would need 16
-// nodes sharing one multiplier layout, which their per-node relaxation choices do not allow.
+// ~100 dependent passes through it, so the kernel is latency / issue bound.  The optimisation loop
+// also exists batched on MFMA, 16 nodes of one network as the 16 columns (they share W; their
+// multipliers are the B operand, the relaxation is elementwise on the accumulators):
+// csrc/beta_opt16.hip, opt-in; this kernel then runs at iters = 0 as its second phase.
 #include <float.h>
 
 #include <algorithm>
@@ -510,6 +512,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FA_BETA_WPE
   // every neuron's state (par / cur / Adam moments, the pgap sums) is touched by the SAME lane
   // everywhere (lane j of its layer, j mod 64), so no lane reads a global word another lane of the
   // wave wrote (the scores and the split neuron's binit use that mapping too)
+  const float* pg = (a.pgsum && a.pgn) ? a.pgsum + (size_t)r * 4 * NH : nullptr;
   for (int l = 0; l < L - 1; ++l)
     for (int j = lane; j < nd.dims[l + 1]; j += 64)
       for (int q = 0; q < 4; ++q) {
@@ -520,10 +523,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FA_BETA_WPE
         if (a.feas) cur[12 * NH + k] = cur[k];          // best iterate of the pass
         mom[k] = 0.f;
         vel[k] = 0.f;
-        S.zb[0][k - q * NH] = 0.f;     // (q-invariant: the sums of neuron nd.neuron_off[l] + j)
-        S.zb[1][k - q * NH] = 0.f;
-        S.hb[0][k - q * NH] = 0.f;
-        S.hb[1][k - q * NH] = 0.f;
+        // (q-invariant: the sums of neuron nd.neuron_off[l] + j; two-phase level: the optimiser's)
+        const int kn = k - q * NH;
+        S.zb[0][kn] = pg ? pg[kn] : 0.f;
+        S.zb[1][kn] = pg ? pg[NH + kn] : 0.f;
+        S.hb[0][kn] = pg ? pg[2 * NH + kn] : 0.f;
+        S.hb[1][kn] = pg ? pg[3 * NH + kn] : 0.f;
       }
   float tc = a.t[r], tbest = tc, mt = 0.f, vt = 0.f;
   // orientation: the objective og (t N_A - (1 - t) N_B) rules out N_A < 0 < N_B (og = +1) or the reverse;
@@ -548,7 +553,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FA_BETA_WPE
   float p1 = 1.f, p2 = 1.f, dk = 1.f;
   // primal iterates summed (pgap): weight 1 (mode 1), it + 1 (mode 2: later iterates count more), or
   // 1 on the second half of the steps only (mode 3)
-  float nacc = 0.f;
+  float nacc = pg ? a.pgn[r] : 0.f;
   for (int it = 0; it < a.iters; ++it) {
     const float kA = bwd<float, false, true, WTL>(nd, Wf, Wt, S, 0, og * tc, cur, cur + 2 * NH, -1, 0, cA, nullptr,
                                                   nullptr);

@@ -33,6 +33,9 @@ extern "C" int fa_bounds_launch(const NetDesc& net, BoundArgs args, hipStream_t 
 extern "C" int fa_point_try_launch(const NetDesc& net, BoundArgs a, hipStream_t stream);
 extern "C" int fa_refine_launch(const NetDesc& net, BoundArgs a, hipStream_t stream);
 extern "C" int fa_beta_launch(const NetDesc& nd, BetaArgs a, hipStream_t stream);
+extern "C" int fa_beta_opt16_fits(const NetDesc& nd);
+extern "C" size_t fa_beta_opt16_scratch_floats(const NetDesc& nd, int R);
+extern "C" int fa_beta_level16_launch(const NetDesc& nd, BetaArgs a, hipStream_t stream);
 extern "C" int fa_bb_count_launch(BetaPoolArgs a, hipStream_t s);
 extern "C" int fa_bb_rows_launch(BetaPoolArgs a, hipStream_t s);
 extern "C" int fa_bb_intersect_launch(BetaPoolArgs a, hipStream_t s);
@@ -146,6 +149,16 @@ class BetaRuntime {
     const int stall = cfg["stall"].cast<int>(), pgap = cfg["pgap"].cast<int>();
     const int warm_beta = cfg["warm_beta"].cast<int>(), tighten = cfg["tighten"].cast<int>();
     const int feas_iters = cfg.contains("feas_iters") ? cfg["feas_iters"].cast<int>() : 0;
+    // batched: the two-phase level (csrc/beta_opt16.hip).  A static choice per (network, config): it
+    // never depends on the slice, so verdicts do not depend on grouping
+    batched_ = cfg.contains("batched") && cfg["batched"].cast<int>() != 0;
+    if (batched_) {
+      if (!fa_beta_opt16_fits(net_)) throw std::runtime_error("beta runtime: batched optimiser does not fit this network");
+      const size_t B = (size_t)batch_;
+      scratch_.ensure(std::max(B * 16 * nh_, fa_beta_opt16_scratch_floats(net_, batch_)));
+      pgsum_.ensure(B * 4 * nh_);
+      pgn_.ensure(B);
+    }
     box_lo_ = box_lo.data();
     box_hi_ = box_hi.data();
     status_.ensure(P); nodes_.ensure(P); probed_.ensure(P); part_closed_.ensure(P);
@@ -399,7 +412,16 @@ class BetaRuntime {
     }
     a.osg = pa.osg;
     a.skip = skip_.p;
-    const int rc = fa_beta_launch(net_, a, st);
+    int rc;
+    if (batched_) {
+      a.pgsum = pgsum_.p;
+      a.pgn = pgn_.p;
+      rc = fa_beta_level16_launch(net_, a, st);
+      a.pgsum = nullptr;          // the infeasibility pass stays on the per-node kernel, unseeded
+      a.pgn = nullptr;
+    } else {
+      rc = fa_beta_launch(net_, a, st);
+    }
     if (rc != 0) throw std::runtime_error("fa_beta_kernel launch failed, code " + std::to_string(rc));
     if (feas_iters > 0) {
       // the infeasibility pass on the nodes left open (phase constraints' Lagrangian alone): closes the
@@ -553,6 +575,8 @@ class BetaRuntime {
   const float* box_lo_ = nullptr;
   const float* box_hi_ = nullptr;
   BBuf<uint8_t> skip_, infeas_, probed_, tree_done_;
+  bool batched_ = false;
+  BBuf<float> pgsum_, pgn_;
   BBuf<float> scratch_, xstar_, xpstar_, binit_, rlo_, rhi_, olb_, oub_, Lc_, Uc_, L0_, Le_, U0_, Ue_, lay_lb_,
       lay_ub_, cpts_, pe_lb_, pe_ub_;
   BBuf<double> bound_;

@@ -41,6 +41,10 @@ extern "C" int fa_decode_launch(const DecodeDesc& d, const int64_t* ids, int P, 
 extern "C" int fa_trace_marker_launch(int tag, int* sink, hipStream_t stream);
 extern "C" int fa_beta_launch(const NetDesc& nd, BetaArgs a, hipStream_t stream);
 extern "C" int fa_beta_config(const NetDesc& nd, int* wpb, int* wtl, size_t* bytes);
+extern "C" int fa_beta_opt16_fits(const NetDesc& nd);
+extern "C" size_t fa_beta_opt16_scratch_floats(const NetDesc& nd, int R);
+extern "C" int fa_beta_opt16_launch(const NetDesc& nd, BetaArgs a, float* pgsum, float* pgn, hipStream_t stream);
+extern "C" int fa_beta_level16_launch(const NetDesc& nd, BetaArgs a, hipStream_t stream);
 extern "C" int fa_knn_launch(const float* X, int n, int d, int k, int* idx, float* dist, hipStream_t stream);
 extern "C" int fa_actdiff_launch(const NetDesc& net, const float* flat, const float* x, const float* xp, int npairs,
                                  float* sum_out, hipStream_t stream);
@@ -510,14 +514,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("trace_marker", [](int tag, uintptr_t sink, uintptr_t stream) {
     check(fa_trace_marker_launch(tag, P<int>(sink), (hipStream_t)stream), "trace_marker");
   });
-  m.def("beta_level", [](const Net& net, uintptr_t flat, uintptr_t wt, int R, std::vector<int> pa, uintptr_t lo,
-                         uintptr_t hi, uintptr_t va, uintptr_t vb, uintptr_t LBA, uintptr_t UBA, uintptr_t LBB,
-                         uintptr_t UBB, uintptr_t phA, uintptr_t phB, uintptr_t par, uintptr_t t, uintptr_t scratch,
-                         int iters, float lr_a, float lr_b, float lr_t, float decay, int lookahead, int beta_pos,
-                         int stall,
-                         uintptr_t bound, uintptr_t split, uintptr_t xstar, uintptr_t binit,
-                         unsigned long long ramask, uintptr_t plo, uintptr_t phi, uintptr_t xpstar, uintptr_t gtie,
-                         float tau, uintptr_t osg, uintptr_t stream) {
+  // the arguments of one beta level (beta_level and the batched entry points share them)
+  auto beta_args = [](const Net& net, uintptr_t flat, uintptr_t wt, int R, const std::vector<int>& pa, uintptr_t lo,
+                      uintptr_t hi, uintptr_t va, uintptr_t vb, uintptr_t LBA, uintptr_t UBA, uintptr_t LBB,
+                      uintptr_t UBB, uintptr_t phA, uintptr_t phB, uintptr_t par, uintptr_t t, uintptr_t scratch,
+                      int iters, float lr_a, float lr_b, float lr_t, float decay, int lookahead, int beta_pos,
+                      int stall, uintptr_t bound, uintptr_t split, uintptr_t xstar, uintptr_t binit,
+                      unsigned long long ramask, uintptr_t plo, uintptr_t phi, uintptr_t xpstar, uintptr_t gtie,
+                      float tau, uintptr_t osg) {
     if (pa.size() > FA_MAX_PA) throw std::invalid_argument("beta_level: too many PA dims");
     for (size_t q = 0; q < pa.size(); ++q)
       if (pa[q] < 0 || pa[q] >= net.d.dims[0] || (q && pa[q] <= pa[q - 1]))
@@ -565,8 +569,54 @@ PYBIND11_MODULE(_C, m) {
     a.osg = P<const int8_t>(osg);
     if ((net.d.dims[0] < 64 && (ramask >> net.d.dims[0])) || (ramask && (!plo || !phi)))
       throw std::invalid_argument("beta_level: RA mask beyond the inputs or no x' box");
+    return a;
+  };
+  m.def("beta_level", [beta_args](const Net& net, uintptr_t flat, uintptr_t wt, int R, std::vector<int> pa,
+                                  uintptr_t lo, uintptr_t hi, uintptr_t va, uintptr_t vb, uintptr_t LBA,
+                                  uintptr_t UBA, uintptr_t LBB, uintptr_t UBB, uintptr_t phA, uintptr_t phB,
+                                  uintptr_t par, uintptr_t t, uintptr_t scratch, int iters, float lr_a, float lr_b,
+                                  float lr_t, float decay, int lookahead, int beta_pos, int stall, uintptr_t bound,
+                                  uintptr_t split, uintptr_t xstar, uintptr_t binit, unsigned long long ramask,
+                                  uintptr_t plo, uintptr_t phi, uintptr_t xpstar, uintptr_t gtie, float tau,
+                                  uintptr_t osg, uintptr_t stream) {
+    const BetaArgs a = beta_args(net, flat, wt, R, pa, lo, hi, va, vb, LBA, UBA, LBB, UBB, phA, phB, par, t, scratch,
+                                 iters, lr_a, lr_b, lr_t, decay, lookahead, beta_pos, stall, bound, split, xstar,
+                                 binit, ramask, plo, phi, xpstar, gtie, tau, osg);
     return fa_beta_launch(net.d, a, reinterpret_cast<hipStream_t>(stream));
   });
+  // two-phase level (csrc/beta_opt16.hip): the batched MFMA optimiser, then fa_beta_kernel at iters = 0
+  // seeded with its primal sums pgsum [R, 4, NH] / pgn [R]; scratch must hold
+  // max(R * 12 * NH, beta_opt16_scratch(R)) floats
+  m.def("beta_level16", [beta_args](const Net& net, uintptr_t flat, uintptr_t wt, int R, std::vector<int> pa,
+                                    uintptr_t lo, uintptr_t hi, uintptr_t va, uintptr_t vb, uintptr_t LBA,
+                                    uintptr_t UBA, uintptr_t LBB, uintptr_t UBB, uintptr_t phA, uintptr_t phB,
+                                    uintptr_t par, uintptr_t t, uintptr_t scratch, int iters, float lr_a, float lr_b,
+                                    float lr_t, float decay, int lookahead, int beta_pos, int stall, uintptr_t bound,
+                                    uintptr_t split, uintptr_t xstar, uintptr_t binit, unsigned long long ramask,
+                                    uintptr_t plo, uintptr_t phi, uintptr_t xpstar, uintptr_t gtie, float tau,
+                                    uintptr_t osg, uintptr_t pgsum, uintptr_t pgn, uintptr_t stream) {
+    BetaArgs a = beta_args(net, flat, wt, R, pa, lo, hi, va, vb, LBA, UBA, LBB, UBB, phA, phB, par, t, scratch, iters,
+                           lr_a, lr_b, lr_t, decay, lookahead, beta_pos, stall, bound, split, xstar, binit, ramask,
+                           plo, phi, xpstar, gtie, tau, osg);
+    a.pgsum = P<const float>(pgsum);
+    a.pgn = P<const float>(pgn);
+    return fa_beta_level16_launch(net.d, a, reinterpret_cast<hipStream_t>(stream));
+  });
+  // phase 1 alone: par / t / gtie optimised in place (best iterate), pgsum / pgn written
+  m.def("beta_opt16", [beta_args](const Net& net, uintptr_t flat, int R, std::vector<int> pa, uintptr_t lo,
+                                  uintptr_t hi, uintptr_t va, uintptr_t vb, uintptr_t LBA, uintptr_t UBA,
+                                  uintptr_t LBB, uintptr_t UBB, uintptr_t phA, uintptr_t phB, uintptr_t par,
+                                  uintptr_t t, uintptr_t scratch, int iters, float lr_a, float lr_b, float lr_t,
+                                  float decay, int beta_pos, int pgap, unsigned long long ramask, uintptr_t plo,
+                                  uintptr_t phi, uintptr_t gtie, float tau, uintptr_t osg, uintptr_t pgsum,
+                                  uintptr_t pgn, uintptr_t stream) {
+    const BetaArgs a = beta_args(net, flat, 0, R, pa, lo, hi, va, vb, LBA, UBA, LBB, UBB, phA, phB, par, t, scratch,
+                                 iters, lr_a, lr_b, lr_t, decay, 0, beta_pos, (pgap & 3) << 1, 0, 0, 0, 0, ramask,
+                                 plo, phi, 0, gtie, tau, osg);
+    return fa_beta_opt16_launch(net.d, a, P<float>(pgsum), P<float>(pgn), reinterpret_cast<hipStream_t>(stream));
+  });
+  m.def("beta_batched_fits", [](const Net& net) { return fa_beta_opt16_fits(net.d) != 0; });
+  m.def("beta_opt16_scratch", [](const Net& net, int R) { return fa_beta_opt16_scratch_floats(net.d, R); });
   m.def("beta_config", [](const Net& net) {
     int w = 0, t = 0;
     size_t b = 0;

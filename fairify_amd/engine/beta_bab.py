@@ -85,6 +85,13 @@ class BetaConfig:
     #                                  pass of this many steps (the phase constraints' Lagrangian alone,
     #                                  ops/beta.py:feasibility_ref) -- the verified LP closes most of its
     #                                  tree as infeasible regions two or three phase splits deep
+    batched: bool = os.environ.get("FAIRIFY_BETA_BATCHED", "0") == "1"
+    #                                  HIP device: the two-phase level -- the optimisation steps on MFMA, 16
+    #                                  nodes per wave (csrc/beta_opt16.hip), then the per-node kernel at
+    #                                  iters = 0 (rigorous bound, branching).  Used when the network fits
+    #                                  the batched kernel (a static choice per network and config, never per
+    #                                  level: verdicts do not depend on grouping); the infeasibility pass
+    #                                  stays per node; the CPU backend runs the torch reference unchanged
     trees: tuple = ()                # experiment: only the trees (ordered-pair row, orientation) listed
     sign_prune: bool = True          # close the (pair, orientation) trees a per-value logit sign test settles
     #                                  before their roots are bounded
@@ -235,6 +242,7 @@ class BetaBaBSolver:
         osg = torch.tensor([1, -1][:O], dtype=torch.int8, device=dev).repeat(run.size * Pp)
         ia, ib = k * V + pr[:, 0], k * V + pr[:, 1]
         self.stats["native"] = self._use_native(O)       # the loop this group runs on (tests / logs)
+        self.stats["batched"] = self._batched()
         if cfg.trees:        # experiment: one tree at a time (tools/exp/beta_vs_lp.py)
             jj = torch.arange(Pp, device=dev).repeat_interleave(O).repeat(run.size)
             sel = torch.zeros_like(k, dtype=torch.bool)
@@ -333,7 +341,7 @@ class BetaBaBSolver:
                                     cfg.beta_pos, rx, pgap=cfg.pgap_weights if cfg.branch == "pgap" else 0,
                                     osg=cur["osg"] if O > 1 else None,
                                     feas_iters=0 if is_root else cfg.feas_iters,
-                                    feas_lr=(cfg.lr_a, cfg.lr_b, cfg.lr_t))
+                                    feas_lr=(cfg.lr_a, cfg.lr_b, cfg.lr_t), batched=self._batched())
             if empty is not None:
                 lev.bound = torch.where(empty, torch.full_like(lev.bound, float("inf")), lev.bound)
             closed = lev.bound >= 0
@@ -401,6 +409,14 @@ class BetaBaBSolver:
         self.stats["nodes"] = self.stats.get("nodes", 0) + int(nodes_np.sum())
         return status, cex_x, cex_xp, nodes_np
 
+    def _batched(self) -> bool:
+        """The two-phase level (BetaConfig.batched): on, a HIP device, and the network fits."""
+        if not (self.cfg.batched and self.be.hip):
+            return False
+        from ..ops import hip
+
+        return hip.beta_batched_fits(self.be)
+
     def _use_native(self, O: int) -> bool:
 
         cfg = self.cfg
@@ -438,7 +454,8 @@ class BetaBaBSolver:
                 "lr_b": float(cfg.lr_b), "lr_t": float(cfg.lr_t), "child_lr": float(cfg.child_lr),
                 "decay": float(cfg.decay), "lookahead": int(cfg.lookahead), "beta_pos": int(bool(cfg.beta_pos)),
                 "stall": 1, "pgap": int(cfg.pgap_weights) if cfg.branch == "pgap" else 0, "warm_beta": int(bool(cfg.warm_beta)),
-                "tighten": int(bool(cfg.tighten)), "feas_iters": int(cfg.feas_iters)}
+                "tighten": int(bool(cfg.tighten)), "feas_iters": int(cfg.feas_iters),
+                "batched": int(self._batched())}
 
         def confirm(parts: np.ndarray, buf: np.ndarray) -> np.ndarray:
             X = np.rint(buf[:, :n0]).astype(np.int64)

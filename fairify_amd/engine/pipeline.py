@@ -168,6 +168,9 @@ class VerifyConfig:
                                          # in the fixed pass: off -- at its 128-node budget with the probe
                                          # it decided nothing more (relaxed/BM BM-8 17 866 vs 18 234 UNKNOWN,
                                          # profiles/r6/); the anytime rounds (growing budgets) run 64 steps
+    beta_batched: bool = os.environ.get("FAIRIFY_BETA_BATCHED", "0") == "1"
+                                         # two-phase beta level: the optimisation on MFMA, 16 nodes per wave
+                                         # (BetaConfig.batched, csrc/beta_opt16.hip); opt-in
     beta_escalate_cap: int = int(os.environ.get("FAIRIFY_BETA_ESC_CAP", "0"))
                                          # networks the beta fixed pass runs on: cap the input-split
                                          # escalation budget at this (their residue goes to beta instead
@@ -324,7 +327,8 @@ def _beta_round(be, q, mlp, unk, lo_np, hi_np, budget, time_budget, batch_nodes,
             branch, iters = ("pgap", cfg.beta_iters) if pairs.shape[0] <= 2 else ("kernel", 64)
         kw = dict(branch=branch, iters=iters, root_iters=max(200, 3 * iters),
                   lookahead=cfg.beta_lookahead, decay=cfg.beta_decay,
-                  feas_iters=max(cfg.beta_feas_iters, 64) if anytime else cfg.beta_feas_iters)
+                  feas_iters=max(cfg.beta_feas_iters, 64) if anytime else cfg.beta_feas_iters,
+                  batched=cfg.beta_batched)
     bs = BetaBaBSolver(be, q, BetaConfig(node_budget=budget, batch_nodes=min(batch_nodes, 32768),
                                          time_budget=time_budget, probe_levels=probe_levels, **kw),
                        **({"timer": tm} if tm is not None else {}))

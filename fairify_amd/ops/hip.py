@@ -633,13 +633,84 @@ def _beta_wt(be) -> torch.Tensor:
     return wt
 
 
+def beta_batched_fits(be) -> bool:
+    """Can the batched optimiser (``fa_beta_opt16_kernel``, csrc/beta_opt16.hip) run this network?
+    (hidden widths <= 112, inputs <= 32, a single logit, both operand orders of W within LDS)"""
+    return bool(ext().beta_batched_fits(_net(be)))
+
+
+def _rx_args(rx, R, n0):
+    """(ramask, plo, phi, gtie [R, 2, n0] or None, tau) of a relaxed level's ``rx`` tuple."""
+    ramask, plo_c, phi_c, gt, tau = 0, None, None, None, 0.0
+    if rx is not None:          # relaxed: copy B's RA dims over [plo, phi]
+        for d in torch.nonzero(rx[0].cpu()).flatten().tolist():
+            ramask |= 1 << int(d)
+        plo_c = _c(rx[1], torch.float32, (R, n0), "plo")
+        phi_c = _c(rx[2], torch.float32, (R, n0), "phi")
+        if len(rx) > 3 and rx[4] is not None:       # the tau tie's multipliers (in / out)
+            tau = float(rx[3])
+            for x, nm in ((rx[4], "gP"), (rx[5], "gM")):
+                if tuple(x.shape) != (R, n0) or x.dtype != torch.float32:
+                    raise ValueError(f"{nm}: expected float32 [{R}, {n0}]")
+            gt = torch.stack([rx[4], rx[5]], 1).contiguous()       # [R, 2, n0]
+    return ramask, plo_c, phi_c, gt, tau
+
+
+def beta_opt16(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, beA, beB, t, iters, lr_a, lr_b, lr_t,
+               decay=1.0, beta_pos=True, rx=None, pgap=0, osg=None):
+    """Phase 1 of the batched level alone (``fa_beta_opt16_kernel``): projected Adam on 16 nodes per
+    wave.  Nothing is modified in place; returns ``(par [R, 4, NH], t [R], gP, gM ([R, n0] or None),
+    pgsum [R, 4, NH], pgn [R])`` -- the best iterate (alpha_A, alpha_B, beta_A, beta_B), its pair
+    weight and tie multipliers, and the weighted primal sums (zA, zB, hA, hB) with their weight sum."""
+    R, n0 = lo.shape
+    NH = be.n_hidden
+    dev = lo.device
+    npa = len(pa)
+    if list(pa) != sorted(pa):
+        raise ValueError("beta_opt16: PA dims must be increasing")
+    if not beta_batched_fits(be):
+        raise RuntimeError("fa_beta_opt16_kernel: network not supported by the batched beta optimiser")
+    f32 = dict(dtype=torch.float32, device=dev)
+    lo_c = _c(lo, torch.float32, (R, n0), "lo")
+    hi_c = _c(hi, torch.float32, (R, n0), "hi")
+    va_c = _c(va, torch.float32, (R, npa), "va")
+    vb_c = _c(vb, torch.float32, (R, npa), "vb")
+    bnd = [_c(x, torch.float32, (R, NH), nm) for x, nm in ((LBA, "LBA"), (UBA, "UBA"), (LBB, "LBB"), (UBB, "UBB"))]
+    pA = _c(phA, torch.int8, (R, NH), "phA")
+    pB = _c(phB, torch.int8, (R, NH), "phB")
+    for x, nm in ((alA, "alA"), (alB, "alB"), (beA, "beA"), (beB, "beB")):
+        if tuple(x.shape) != (R, NH) or x.dtype != torch.float32:
+            raise ValueError(f"{nm}: expected float32 [{R}, {NH}]")
+    if tuple(t.shape) != (R,) or t.dtype != torch.float32:
+        raise ValueError("t: expected float32 [R]")
+    par = torch.stack([alA, alB, beA, beB], 1).contiguous()
+    t_o = t.clone().contiguous()
+    ramask, plo_c, phi_c, gt, tau = _rx_args(rx, R, n0)
+    osg_c = None if osg is None else _c(osg, torch.int8, (R,), "osg")
+    pgsum = torch.zeros(R, 4, NH, **f32)
+    pgn = torch.zeros(R, **f32)
+    if R:
+        scratch = torch.empty(max(int(ext().beta_opt16_scratch(_net(be), R)), 1), **f32)
+        rc = ext().beta_opt16(_net(be), be.flat.data_ptr(), R, [int(d) for d in pa], lo_c.data_ptr(), hi_c.data_ptr(),
+                              va_c.data_ptr(), vb_c.data_ptr(), *[x.data_ptr() for x in bnd], pA.data_ptr(),
+                              pB.data_ptr(), par.data_ptr(), t_o.data_ptr(), scratch.data_ptr(), int(iters),
+                              float(lr_a), float(lr_b), float(lr_t), float(decay), int(bool(beta_pos)), int(pgap),
+                              int(ramask), _ptr(plo_c), _ptr(phi_c), _ptr(gt), float(tau), _ptr(osg_c),
+                              pgsum.data_ptr(), pgn.data_ptr(), _stream(dev))
+        if rc != 0:
+            raise RuntimeError(f"fa_beta_opt16_kernel launch failed ({rc})")
+    return par, t_o, (None if gt is None else gt[:, 0]), (None if gt is None else gt[:, 1]), pgsum, pgn
+
+
 def beta_level(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, beA, beB, t, iters, lr_a, lr_b, lr_t,
                decay=1.0, lookahead=0, beta_pos=True, rx=None, stall=True, pgap=False, osg=None, feas_iters=0,
-               feas_lr=None):
+               feas_lr=None, batched=False):
     """One beta-CROWN BaB level on the device (``fa_beta_kernel``, csrc/beta.hip): the rows'
     (alpha, beta, t) are optimised IN PLACE (kept at the best iterate) and their rigorous fp64
     bounds, branching decisions, concretising vertices and child multipliers returned
-    (:class:`ops.beta.BetaLevel`)."""
+    (:class:`ops.beta.BetaLevel`).  ``batched``: the two-phase level -- the optimisation on MFMA, 16
+    nodes per wave (csrc/beta_opt16.hip), then this kernel at ``iters = 0`` for the rigorous bound and
+    the branching; a network the batched kernel cannot run raises."""
     from . import beta as B
 
     R, n0 = lo.shape
@@ -662,36 +733,36 @@ def beta_level(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, b
     if tuple(t.shape) != (R,) or t.dtype != torch.float32 or not t.is_contiguous():
         raise ValueError("t: expected contiguous float32 [R]")
     par = torch.stack([alA, alB, beA, beB], 1).contiguous()          # [R, 4, NH]
-    scratch = torch.empty(R, 16 if feas_iters > 0 else 12, NH, **f32)
+    nscr = R * (16 if feas_iters > 0 else 12) * NH
+    pgsum = pgn = None
+    if batched:
+        if not beta_batched_fits(be):
+            raise RuntimeError("fa_beta_opt16_kernel: network not supported by the batched beta optimiser")
+        nscr = max(nscr, int(ext().beta_opt16_scratch(_net(be), R)))
+        pgsum = torch.empty(R, 4, NH, **f32)
+        pgn = torch.empty(R, **f32)
+    scratch = torch.empty(max(nscr, 1), **f32)
     bound = torch.empty(R, dtype=torch.float64, device=dev)
     split = torch.empty(R, dtype=torch.int32, device=dev)
     xstar = torch.empty(R, n0, **f32)
     binit = torch.empty(R, 2, **f32)
     xpstar = torch.empty(R, n0, **f32)
-    ramask, plo_c, phi_c, gt, tau = 0, None, None, None, 0.0
-    if rx is not None:          # relaxed: copy B's RA dims over [plo, phi]
-        for d in torch.nonzero(rx[0].cpu()).flatten().tolist():
-            ramask |= 1 << int(d)
-        plo_c = _c(rx[1], torch.float32, (R, n0), "plo")
-        phi_c = _c(rx[2], torch.float32, (R, n0), "phi")
-        if len(rx) > 3 and rx[4] is not None:       # the tau tie's multipliers (in / out)
-            tau = float(rx[3])
-            for x, nm in ((rx[4], "gP"), (rx[5], "gM")):
-                if tuple(x.shape) != (R, n0) or x.dtype != torch.float32:
-                    raise ValueError(f"{nm}: expected float32 [{R}, {n0}]")
-            gt = torch.stack([rx[4], rx[5]], 1).contiguous()       # [R, 2, n0]
+    ramask, plo_c, phi_c, gt, tau = _rx_args(rx, R, n0)
     osg_c = None if osg is None else _c(osg, torch.int8, (R,), "osg")
     if R:
-        def launch(n_it, flags, lra, lrb, lrt):
-            return ext().beta_level(_net(be), be.flat.data_ptr(), _beta_wt(be).data_ptr(), R, [int(d) for d in pa],
-                                    lo_c.data_ptr(), hi_c.data_ptr(), va_c.data_ptr(), vb_c.data_ptr(),
-                                    *[x.data_ptr() for x in bnd], pA.data_ptr(), pB.data_ptr(), par.data_ptr(),
-                                    t.data_ptr(), scratch.data_ptr(), int(n_it), float(lra), float(lrb), float(lrt),
-                                    float(decay), int(lookahead), int(bool(beta_pos)), flags, bound.data_ptr(),
-                                    split.data_ptr(), xstar.data_ptr(), binit.data_ptr(), int(ramask), _ptr(plo_c),
-                                    _ptr(phi_c), xpstar.data_ptr(), _ptr(gt), float(tau), _ptr(osg_c), _stream(dev))
+        def launch(n_it, flags, lra, lrb, lrt, two_phase=False):
+            args = (_net(be), be.flat.data_ptr(), _beta_wt(be).data_ptr(), R, [int(d) for d in pa],
+                    lo_c.data_ptr(), hi_c.data_ptr(), va_c.data_ptr(), vb_c.data_ptr(),
+                    *[x.data_ptr() for x in bnd], pA.data_ptr(), pB.data_ptr(), par.data_ptr(),
+                    t.data_ptr(), scratch.data_ptr(), int(n_it), float(lra), float(lrb), float(lrt),
+                    float(decay), int(lookahead), int(bool(beta_pos)), flags, bound.data_ptr(),
+                    split.data_ptr(), xstar.data_ptr(), binit.data_ptr(), int(ramask), _ptr(plo_c),
+                    _ptr(phi_c), xpstar.data_ptr(), _ptr(gt), float(tau), _ptr(osg_c))
+            if two_phase:
+                return ext().beta_level16(*args, pgsum.data_ptr(), pgn.data_ptr(), _stream(dev))
+            return ext().beta_level(*args, _stream(dev))
 
-        rc = launch(iters, int(bool(stall)) | (int(pgap) << 1), lr_a, lr_b, lr_t)
+        rc = launch(iters, int(bool(stall)) | (int(pgap) << 1), lr_a, lr_b, lr_t, two_phase=bool(batched))
         if rc == 0 and feas_iters > 0:
             # the infeasibility pass (bit 3) on the nodes left open: only their bounds can change
             rc = launch(feas_iters, 8, *(feas_lr or (lr_a, lr_b, lr_t)))

@@ -1,0 +1,450 @@
+"""The batched beta-CROWN optimiser (csrc/beta_opt16.hip: 16 BaB nodes per wave on MFMA) and the
+two-phase level built on it (``hip.beta_level(batched=True)``: the optimiser, then fa_beta_kernel at
+iters = 0) against the PyTorch reference (ops/beta.py:level_ref), brute-force lattice enumeration and
+the per-node kernel."""
+import numpy as np
+import pytest
+import torch
+
+from fairify_amd import presets
+from fairify_amd.engine import exact
+from fairify_amd.engine.bab import SAT, UNKNOWN
+from fairify_amd.engine.beta_bab import BetaBaBSolver, BetaConfig
+from fairify_amd.models.mlp import random_mlp
+from fairify_amd.models.zoo import get_model
+from fairify_amd.ops import beta as B
+from fairify_amd.ops import ext, hip
+from fairify_amd.ops.backend import Backend
+from fairify_amd.partition import processing_order
+
+from test_beta_bab import _brute_pair, _setup, _true_min
+
+pytestmark = pytest.mark.gpu
+
+LR = dict(lr_a=0.1, lr_b=0.5, lr_t=0.1)
+
+
+def _params(R, NH, seed, neg):
+    g = torch.Generator().manual_seed(seed)
+    al = [torch.rand(R, NH, generator=g) for _ in range(2)]
+    be_ = [torch.rand(R, NH, generator=g) * (2 if neg else 1) - (1 if neg else 0) for _ in range(2)]
+    t = torch.rand(R, generator=g)
+    return al, be_, t
+
+
+def _setup_wide_input(seed, widths=(20, 17, 4), n0=17, R=6, fix=0.1):
+    """``_setup`` for n0 > 4 (its box pattern is four dims long): two input tiles, the second ragged."""
+    g = np.random.default_rng(seed)
+    m = random_mlp(n0, list(widths), seed=seed, bias_scale=0.5)
+    ws = [torch.tensor(np.asarray(w), dtype=torch.float32) for w in m.weights]
+    bs = [torch.tensor(np.asarray(b), dtype=torch.float32).reshape(-1) for b in m.biases]
+    pa = [1]
+    lo = np.tile(np.resize(np.array([0, 0, 1, -2], np.float32), n0), (R, 1))
+    hi = lo + g.integers(0, 2, size=(R, n0)).astype(np.float32)
+    lo[:, pa] = 0
+    hi[:, pa] = 1
+    va = np.zeros((R, 1), np.float32)
+    vb = np.ones((R, 1), np.float32)
+    be = Backend(m)
+    NH = be.n_hidden
+    out = []
+    for v in (va, vb):
+        rl, rh = lo.copy(), hi.copy()
+        rl[:, pa] = v
+        rh[:, pa] = v
+        res = be.bounds(torch.from_numpy(rl), torch.from_numpy(rh), keep_layers=True)
+        out.append((torch.cat(res.layer_lb, 1)[:, :NH].float(), torch.cat(res.layer_ub, 1)[:, :NH].float()))
+    ph = []
+    for c in range(2):
+        p = g.integers(-1, 2, size=(R, NH)) * (g.random((R, NH)) < fix)
+        ph.append(torch.from_numpy(p.astype(np.int8)))
+    return m, ws, bs, pa, torch.from_numpy(lo), torch.from_numpy(hi), torch.from_numpy(va), torch.from_numpy(vb), out, ph
+
+
+def _relax(S, seed, tie):
+    """The relaxed variant of a ``_setup`` tuple (RA dim 2 widened by one for x', copy B's partition
+    bounds over that box; tie: random start multipliers), as
+    test_beta_gpu.py::test_beta_kernel_relaxed_matches_reference_and_is_sound builds it."""
+    m, ws, bs, pa, lo, hi, va, vb, bnd, ph = S
+    R, n0 = lo.shape
+    NH = bnd[0][0].shape[1]
+    ra = [2]
+    ram = torch.zeros(n0, dtype=torch.bool)
+    ram[ra] = True
+    plo, phi = lo.clone(), hi.clone()
+    plo[:, ra] -= 1
+    phi[:, ra] += 1
+    rl, rh = plo.clone(), phi.clone()
+    rl[:, pa] = vb
+    rh[:, pa] = vb
+    rb = Backend(m).bounds(rl, rh, keep_layers=True)
+    bnd = [bnd[0], (torch.cat(rb.layer_lb, 1)[:, :NH].float(), torch.cat(rb.layer_ub, 1)[:, :NH].float())]
+    g = torch.Generator().manual_seed(seed + 100)
+    gP = torch.rand(R, n0, generator=g) * ram.float()
+    gM = torch.rand(R, n0, generator=g) * ram.float()
+    rx = (ram, plo, phi, 1.0, gP, gM) if tie else (ram, plo, phi)
+    return (m, ws, bs, pa, lo, hi, va, vb, bnd, ph), rx, ra
+
+
+def _rx_to(rx, f):
+    if rx is None:
+        return None
+    return (rx[0],) + tuple(f(x.clone()) for x in rx[1:3]) + ((rx[3],) + tuple(f(x.clone()) for x in rx[4:6])
+                                                              if len(rx) > 3 else ())
+
+
+def _level_pair(cuda, S, seed, iters, neg=False, lookahead=0, pgap=0, rx=None, osg=None, batched=True, ref=True):
+    """One level through the reference (CPU) and through hip.beta_level: (ref level, GPU level, ref
+    parameters, GPU parameters (alA, alB, beA, beB, t), GPU rx)."""
+    m, ws, bs, pa, lo, hi, va, vb, bnd, ph = S
+    R = lo.shape[0]
+    w = [x.shape[1] for x in ws[:-1]]
+    NH = sum(w)
+    al, be_, t = _params(R, NH, seed, neg)
+    cpu = [x.clone() for x in (al[0], al[1], be_[0], be_[1], t)]
+    lr_ = None
+    if ref:
+        lr_ = B.level_ref(ws, bs, w, lo, hi, pa, va, vb, bnd[0][0], bnd[0][1], bnd[1][0], bnd[1][1], ph[0], ph[1],
+                          *cpu, iters=iters, lookahead=lookahead, beta_pos=not neg, pgap=pgap,
+                          rx=_rx_to(rx, lambda x: x), osg=osg, **LR)
+    d = lambda x: x.to(cuda).contiguous()  # noqa: E731
+    gpu = [d(x.clone()) for x in (al[0], al[1], be_[0], be_[1], t)]
+    rxg = _rx_to(rx, d)
+    lg = hip.beta_level(Backend(m, cuda), d(lo), d(hi), pa, d(va), d(vb), d(bnd[0][0]), d(bnd[0][1]), d(bnd[1][0]),
+                        d(bnd[1][1]), d(ph[0]), d(ph[1]), *gpu, iters=iters, lookahead=lookahead, beta_pos=not neg,
+                        pgap=pgap, rx=rxg, osg=None if osg is None else d(osg), batched=batched, **LR)
+    torch.cuda.synchronize()
+    return lr_, lg, cpu, [x.cpu() for x in gpu], rxg
+
+
+def _opt16(cuda, S, seed, iters, rows=None, pgap=1, rx=None, neg=False):
+    """hip.beta_opt16 on the rows ``rows`` (default all) of a setup: CPU copies of its outputs."""
+    m, ws, bs, pa, lo, hi, va, vb, bnd, ph = S
+    R = lo.shape[0]
+    NH = bnd[0][0].shape[1]
+    al, be_, t = _params(R, NH, seed, neg)
+    idx = torch.arange(R) if rows is None else torch.as_tensor(rows)
+    d = lambda x: x[idx].to(cuda).contiguous()  # noqa: E731
+    rxg = None
+    if rx is not None:
+        rxg = (rx[0], d(rx[1]), d(rx[2])) + ((rx[3], d(rx[4]), d(rx[5])) if len(rx) > 3 else ())
+    out = hip.beta_opt16(Backend(m, cuda), d(lo), d(hi), pa, d(va), d(vb), d(bnd[0][0]), d(bnd[0][1]), d(bnd[1][0]),
+                         d(bnd[1][1]), d(ph[0]), d(ph[1]), d(al[0]), d(al[1]), d(be_[0]), d(be_[1]), d(t), iters,
+                         LR["lr_a"], LR["lr_b"], LR["lr_t"], beta_pos=not neg, rx=rxg, pgap=pgap)
+    torch.cuda.synchronize()
+    start = (torch.stack([al[0], al[1], be_[0], be_[1]], 1)[idx], t[idx])
+    return [None if x is None else x.cpu() for x in out], start
+
+
+# ---------------------------------------------------------------------------------------------- 1
+@pytest.mark.parametrize("widths,R", [((6, 5, 4), 6), ((20, 17, 4), 17)])
+@pytest.mark.parametrize("tie", [False, True])
+def test_opt16_one_step_returns_the_start(cuda, widths, R, tie):
+    """iters = 1: the best iterate is evaluated before the update, so par / t / the tie multipliers
+    come back bitwise equal to the inputs, and pgn is the first step's weight (1) for every node the
+    step left open.  (20, 17, 4) with 17 nodes: ragged row tiles in M and K, two wave groups, the
+    last with one column."""
+    S = _setup(4, widths=widths, R=R, fix=0.1)
+    rx = None
+    if tie:
+        S, rx, _ = _relax(S, 4, True)
+    (par, t, gP, gM, pgsum, pgn), (par0, t0) = _opt16(cuda, S, 4, 1, rx=rx)
+    assert torch.equal(par, par0)
+    assert torch.equal(t, t0)
+    if tie:
+        assert torch.equal(gP, rx[4]) and torch.equal(gM, rx[5])
+    # the rigorous bound at the start: well below 0 -> the node was stepped once; empty region -> never
+    _, lg0, _, _, _ = _level_pair(cuda, S, 4, 0, rx=rx, batched=False, ref=False)
+    b0 = lg0.bound.cpu()
+    stepped = torch.isfinite(b0) & (b0 < -1e-3)
+    assert int(stepped.sum()) > 0
+    assert bool((pgn[stepped] == 1.0).all())
+    assert bool((pgn[~torch.isfinite(b0)] == 0.0).all())
+    assert bool(((pgn == 0.0) | (pgn == 1.0)).all())
+    assert bool((pgsum[pgn == 0.0] == 0.0).all())
+
+
+# ---------------------------------------------------------------------------------------------- 2
+def _check_split(lr_, lg):
+    sg, sr, sc = lg.split.cpu(), lr_.split, lr_.scores
+    n_neu = 0
+    for r in range(sg.numel()):
+        if not torch.isfinite(lr_.bound[r]) or lr_.bound[r] >= 0:
+            continue
+        if sr[r] >= 0:
+            n_neu += 1
+            assert sg[r] >= 0, (r, int(sg[r]), int(sr[r]))
+            best = float(sc[r].max())
+            assert float(sc[r, sg[r]]) >= best * (1 - 1e-3) - 1e-5, (r, int(sg[r]), int(sr[r]))
+        else:
+            assert int(sg[r]) == int(sr[r]), (r, int(sg[r]), int(sr[r]))
+    return n_neu
+
+
+@pytest.mark.parametrize("seed", [5, 8, 12])
+@pytest.mark.parametrize("pgap", [False, True])
+@pytest.mark.parametrize("neg", [False, True])
+def test_two_phase_few_steps_track_reference(cuda, seed, pgap, neg):
+    """iters = 3 (fp32 trajectories still agree): the two-phase level's rigorous bounds equal the
+    reference's, and it splits a neuron the reference scores best or the same input dim (the
+    assertions of test_beta_gpu.py::test_beta_kernel_primal_gap_split_matches_reference)."""
+    S = _setup(seed, fix=0.1)
+    lr_, lg, _, _, _ = _level_pair(cuda, S, seed, 3, neg=neg, pgap=int(pgap))
+    fin = torch.isfinite(lr_.bound)
+    assert torch.allclose(lg.bound.cpu()[fin], lr_.bound[fin], rtol=1e-5, atol=1e-5)
+    assert _check_split(lr_, lg) > 0
+
+
+@pytest.mark.parametrize("widths,n0", [((20, 17, 4), 17), ((100, 100), 13)])
+def test_two_phase_wide_input_tracks_reference(cuda, widths, n0):
+    """n0 = 17, widths (20, 17, 4): two input tiles (no brute force at that size); AC-4's shape
+    (13-100-100-1): the 7-tile instance with 127 KB of staged weights."""
+    S = _setup_wide_input(5, widths=widths, n0=n0, fix=0.1 if n0 == 17 else 0.005)
+    lr_, lg, _, _, _ = _level_pair(cuda, S, 5, 3, pgap=1)
+    fin = torch.isfinite(lr_.bound)
+    assert int(fin.sum()) > 0
+    assert torch.allclose(lg.bound.cpu()[fin], lr_.bound[fin], rtol=1e-5, atol=1e-5)
+    _check_split(lr_, lg)
+
+
+# ---------------------------------------------------------------------------------------------- 3
+@pytest.mark.parametrize("seed", [3, 4])
+@pytest.mark.parametrize("look", [0, 4])
+def test_two_phase_optimises_soundly(cuda, seed, look):
+    """The assertions of test_beta_gpu.py::test_beta_kernel_optimises_soundly on the batched path."""
+    S = _setup(seed, fix=0.15)
+    m, ws, bs, pa, lo, hi, va, vb, bnd, ph = S
+    w = [x.shape[1] for x in ws[:-1]]
+    lr_, lg, _, gp, _ = _level_pair(cuda, S, seed, 60, lookahead=look)
+    _, lg0, _, _, _ = _level_pair(cuda, S, seed, 0, lookahead=look, ref=False)
+    bg, b0 = lg.bound.cpu(), lg0.bound.cpu()
+    fin = torch.isfinite(b0)
+    assert bool((bg[fin] >= b0[fin] - 1e-5 * (1 + b0[fin].abs())).all())
+    assert bool((bg[fin] > b0[fin] + 1e-3).any())
+    assert float((bg[fin] - lr_.bound[fin]).abs().max()) < 0.05 * (1 + float(lr_.bound[fin].abs().max()))
+    t = gp[4]
+    for r in range(lo.shape[0]):
+        tm = _true_min(m, lo[r].numpy(), hi[r].numpy(), pa, va[r].numpy(), vb[r].numpy(), ph[0][r].numpy(),
+                       ph[1][r].numpy(), float(t[r]), w)
+        assert float(bg[r]) <= tm
+
+
+# ---------------------------------------------------------------------------------------------- 4
+@pytest.mark.parametrize("seed,tie", [(0, False), (2, False), (0, True), (3, True)])
+def test_two_phase_relaxed_matches_reference_and_is_sound(cuda, seed, tie):
+    """Relaxed queries (copy B's RA dim over x''s box, with and without the tie's multipliers) through
+    the batched path.  iters = 0: the checks of
+    test_beta_gpu.py::test_beta_kernel_relaxed_matches_reference_and_is_sound unchanged (the rigorous
+    pass alone, fp64: 1e-9).  iters = 3: the optimiser's fp32 trajectory against the reference's (the
+    few-step tolerance 1e-5), x'* on a face of x''s box, and the bound below the true minimum over the
+    (tie-restricted) pairs at the returned t and multipliers, with zero slack."""
+    from test_beta_gpu import _true_min_rx
+
+    for fix, iters, tol in ((0.3, 0, 1e-9), (0.3, 3, 1e-5), (0.1, 3, 1e-5)):   # (fix 0.1: more non-empty regions)
+        S, rx, ra = _relax(_setup(seed, fix=fix), seed, tie)
+        m, ws, bs, pa, lo, hi, va, vb, bnd, ph = S
+        plo, phi = rx[1], rx[2]
+        lr_, lg, _, gp, _ = _level_pair(cuda, S, seed, iters, rx=rx)
+        bg = lg.bound.cpu()
+        fin = torch.isfinite(lr_.bound)
+        assert torch.allclose(bg[fin], lr_.bound[fin], rtol=tol, atol=tol)
+        xp = lg.xpstar.cpu()[fin][:, ra]
+        if iters == 0:
+            assert torch.equal(xp, lr_.xpstar[fin][:, ra])
+        else:
+            assert bool(((xp == plo[fin][:, ra]) | (xp == phi[fin][:, ra])).all())
+        t = gp[4]
+        for r in range(lo.shape[0]):
+            tm = _true_min_rx(m, lo[r].numpy(), hi[r].numpy(), plo[r].numpy(), phi[r].numpy(), pa, ra,
+                              va[r].numpy(), vb[r].numpy(), ph[0][r].numpy(), ph[1][r].numpy(), float(t[r]),
+                              1.0 if tie else None)
+            assert float(bg[r]) <= tm, (iters, r, float(bg[r]), tm)
+
+
+@pytest.mark.parametrize("seed", [0, 2])
+def test_two_phase_orientation_sign_matches_reference(cuda, seed):
+    """osg = -1 on half the rows (test_beta_gpu.py::test_beta_kernel_orientation_sign_matches_reference),
+    three optimisation steps: the optimiser keeps each node's orientation."""
+    S = _setup(seed)
+    R = S[4].shape[0]
+    osg = torch.tensor([1, -1] * (R // 2) + [1] * (R % 2), dtype=torch.int8)
+    lr_, lg, _, _, _ = _level_pair(cuda, S, seed, 3, osg=osg)
+    fin = torch.isfinite(lr_.bound)
+    assert torch.allclose(lg.bound.cpu()[fin], lr_.bound[fin], rtol=1e-5, atol=1e-5)
+
+
+# ---------------------------------------------------------------------------------------------- 5
+def test_opt16_neighbour_independence(cuda):
+    """A node's outputs are bitwise independent of what shares its wave and of R: nodes 0, 5 and 16 of
+    17 give the same par / t / pgsum / pgn with all 17 nodes, each alone, and with the rows reversed.
+    The seed is picked with level_ref so that the set exercises the freeze rule: node 5 closes during
+    the 40 steps (it freezes while its wave goes on), nodes 0 and 16 stay open."""
+    seed, iters = 28, 40
+    S = _setup(seed, widths=(20, 17, 4), R=17, fix=0.03)
+    m, ws, bs, pa, lo, hi, va, vb, bnd, ph = S
+    R = 17
+    w = [x.shape[1] for x in ws[:-1]]
+
+    def ref(it):
+        al, be_, t = _params(R, sum(w), seed, False)
+        return B.level_ref(ws, bs, w, lo, hi, pa, va, vb, bnd[0][0], bnd[0][1], bnd[1][0], bnd[1][1], ph[0], ph[1],
+                           al[0], al[1], be_[0], be_[1], t, iters=it, pgap=1, **LR).bound
+
+    b0, b40 = ref(0), ref(iters)
+    closes = (b0 < -1e-3) & (b40 > 1e-3) & torch.isfinite(b40)
+    stays = b40 < -1e-3
+    assert bool(closes[5]) and bool(stays[0]) and bool(stays[16])
+    full, _ = _opt16(cuda, S, seed, iters)
+    rev, _ = _opt16(cuda, S, seed, iters, rows=list(range(R - 1, -1, -1)))
+    # the freeze rule ran: the closing node was stepped fewer times than the open ones
+    pgn = full[5]
+    assert float(pgn[5]) < iters and float(pgn[0]) == iters and float(pgn[16]) == iters
+    for k in (0, 5, 16):
+        alone, _ = _opt16(cuda, S, seed, iters, rows=[k])
+        for a, f, rv in zip(alone, full, rev):
+            if a is None:
+                continue
+            assert torch.equal(a[0], f[k]), k
+            assert torch.equal(rv[R - 1 - k], f[k]), k
+
+
+# ---------------------------------------------------------------------------------------------- 6
+def test_second_phase_is_neutral_without_primal_sums(cuda):
+    """Null pgsum / pgn change nothing: hip.beta_level(batched=False) and the original binding give
+    bitwise the same outputs (one process, same inputs); and the two-phase level at iters = 0 (zero
+    sums, zero weight) is bitwise the per-node level at iters = 0."""
+    seed = 3
+    S = _setup(seed)
+    m, ws, bs, pa, lo, hi, va, vb, bnd, ph = S
+    R, n0 = lo.shape
+    NH = bnd[0][0].shape[1]
+    _, lg, _, gp, _ = _level_pair(cuda, S, seed, 3, batched=False, ref=False)
+    # the original binding, called directly
+    be = Backend(m, cuda)
+    d = lambda x: x.to(cuda).contiguous()  # noqa: E731
+    al, be_, t = _params(R, NH, seed, False)
+    par = d(torch.stack([al[0], al[1], be_[0], be_[1]], 1))
+    tt = d(t)
+    ins = [d(x) for x in (lo, hi, va, vb, bnd[0][0], bnd[0][1], bnd[1][0], bnd[1][1], ph[0], ph[1])]
+    scratch = torch.empty(R, 12, NH, device=cuda)
+    bound = torch.empty(R, dtype=torch.float64, device=cuda)
+    split = torch.empty(R, dtype=torch.int32, device=cuda)
+    xstar = torch.empty(R, n0, device=cuda)
+    binit = torch.empty(R, 2, device=cuda)
+    xpstar = torch.empty(R, n0, device=cuda)
+    rc = ext().beta_level(hip._net(be), be.flat.data_ptr(), hip._beta_wt(be).data_ptr(), R, list(pa),
+                          *[x.data_ptr() for x in ins], par.data_ptr(), tt.data_ptr(), scratch.data_ptr(), 3,
+                          LR["lr_a"], LR["lr_b"], LR["lr_t"], 1.0, 0, 1, 1, bound.data_ptr(), split.data_ptr(),
+                          xstar.data_ptr(), binit.data_ptr(), 0, 0, 0, xpstar.data_ptr(), 0, 0.0, 0,
+                          torch.cuda.current_stream(cuda).cuda_stream)
+    torch.cuda.synchronize()
+    assert rc == 0
+    assert torch.equal(bound.cpu(), lg.bound.cpu())
+    assert torch.equal(split.cpu().long(), lg.split.cpu())
+    assert torch.equal(xstar.cpu(), lg.xstar.cpu())
+    assert torch.equal(binit.cpu(), lg.binit.cpu())
+    for q in range(4):
+        assert torch.equal(par[:, q].cpu(), gp[q])
+    assert torch.equal(tt.cpu(), gp[4])
+    for pgap in (0, 1):
+        _, l0, _, g0, _ = _level_pair(cuda, S, seed, 0, pgap=pgap, lookahead=4, batched=False, ref=False)
+        _, l1, _, g1, _ = _level_pair(cuda, S, seed, 0, pgap=pgap, lookahead=4, batched=True, ref=False)
+        assert torch.equal(l0.bound.cpu(), l1.bound.cpu())
+        assert torch.equal(l0.split.cpu(), l1.split.cpu())
+        assert torch.equal(l0.xstar.cpu(), l1.xstar.cpu())
+        assert torch.equal(l0.binit.cpu(), l1.binit.cpu())
+        for a, b in zip(g0, g1):
+            assert torch.equal(a, b)
+
+
+# ---------------------------------------------------------------------------------------------- 7
+# Node budgets: four times the smallest budget of 8, 16, 32, ... at which the per-node path (batched off,
+# the kernel this feature leaves bitwise unchanged -- test 6) decides every partition of the setup,
+# measured once on an MI355X, the same in the native and the torch loop: 32 for the PA-only setups
+# of seed 3 (both branching rules), 8 (the probe's smallest) for seed 6 and for both relaxed setups.
+BUDGETS = {("pa", 3, "kernel"): 4 * 32, ("pa", 6, "kernel"): 4 * 8, ("pa", 3, "pgap"): 4 * 32,
+           ("rx", 21, 2): 4 * 8, ("rx", 24, 3): 4 * 8}
+
+
+@pytest.mark.parametrize("seed,branch", [(3, "kernel"), (6, "kernel"), (3, "pgap")])
+def test_batched_bab_matches_bruteforce(cuda, seed, branch):
+    """BetaBaBSolver with batched=True, native runtime and torch loop (the setup of
+    test_beta_gpu.py::test_beta_bab_gpu_matches_bruteforce): no partition is left UNKNOWN at four times
+    the per-node path's deciding budget, every verdict equals lattice enumeration, both loops agree."""
+    pre = presets.get("src/AC-sex")
+    grid, q = pre.grid(), pre.resolved()
+    ids = processing_order(grid, 0)[:24]
+    lo, hi = grid.decode(ids)
+    hi = np.minimum(hi, lo + 1)
+    m = random_mlp(13, [8, 6, 4], seed=seed, bias_scale=0.5)
+    pa = q.pa_idx[0]
+    out = {}
+    for native in (True, False):
+        sol = BetaBaBSolver(Backend(m, cuda), q, BetaConfig(node_budget=BUDGETS[("pa", seed, branch)], iters=20,
+                                                            root_iters=40, branch=branch, native=native,
+                                                            batched=True))
+        res = sol.solve(lo, hi, m)
+        assert bool(sol.stats.get("native")) == native
+        assert sol.stats.get("batched") is True
+        assert int((res.status == UNKNOWN).sum()) == 0, res.status
+        for k in range(len(ids)):
+            assert (res.status[k] == SAT) == _brute_pair(m, lo[k], hi[k], pa), k
+        sat = np.nonzero(res.status == SAT)[0]
+        if sat.size:
+            assert exact.is_violation(m, res.cex_x[sat], res.cex_xp[sat]).all()
+        out[native] = res.status
+    assert bool((out[True] == out[False]).all())
+
+
+@pytest.mark.parametrize("seed,tau", [(21, 2), (24, 3)])
+def test_batched_bab_relaxed_matches_bruteforce(cuda, seed, tau):
+    """Relaxed twin (test_beta_gpu.py::test_beta_bab_gpu_relaxed_matches_bruteforce): x' RA boxes, tie
+    multipliers and both orientations through the batched optimiser."""
+    from fairify_amd.spec import ADULT, Query
+    from test_beta_bab import _relaxed_truth
+
+    q = Query(pa=("sex",), ra=("age",), tau=tau).resolve(ADULT)
+    grid = presets.get("src/AC-sex").grid()
+    ids = processing_order(grid, 0)[:16]
+    lo, hi = grid.decode(ids)
+    hi = np.minimum(hi, lo + 1)
+    pa, ra = q.pa_idx[0], q.ra_idx[0]
+    m = random_mlp(13, [8, 6, 4], seed=seed, bias_scale=0.5)
+    truth = [_relaxed_truth(m, lo[k], hi[k], pa, ra, tau) for k in range(len(ids))]
+    out = {}
+    for native in (True, False):
+        sol = BetaBaBSolver(Backend(m, cuda), q, BetaConfig(node_budget=BUDGETS[("rx", seed, tau)], iters=20,
+                                                            root_iters=40, branch="kernel", native=native,
+                                                            batched=True))
+        res = sol.solve(lo, hi, m)
+        assert bool(sol.stats.get("native")) == native
+        assert sol.stats.get("batched") is True
+        assert int((res.status == UNKNOWN).sum()) == 0, res.status
+        for k in range(len(ids)):
+            assert (res.status[k] == SAT) == truth[k], k
+            if res.status[k] == SAT:
+                ok = exact.check_pair_constraints(res.cex_x[k:k + 1], res.cex_xp[k:k + 1], lo[k:k + 1],
+                                                  hi[k:k + 1], q.pa_idx, q.ra_idx, q.tau)
+                assert ok[0] and exact.is_violation(m, res.cex_x[k:k + 1], res.cex_xp[k:k + 1])[0]
+        out[native] = res.status
+    assert bool((out[True] == out[False]).all())
+
+
+# ---------------------------------------------------------------------------------------------- 8
+def test_batched_fits(cuda):
+    """The zoo shapes up to 112 wide fit; BM-4 (150 wide, 225 KB of staged weights) does not, and asking
+    for the batched level on it raises (as the per-node kernel does for a network it cannot run)."""
+    for name in ("AC-7", "AC-4", "BM-8"):
+        assert hip.beta_batched_fits(Backend(get_model(name, weights="zoo", seed=0), cuda)), name
+    m = get_model("BM-4", weights="zoo", seed=0)
+    be = Backend(m, cuda)
+    assert not hip.beta_batched_fits(be)
+    n0, NH, R = int(np.asarray(m.weights[0]).shape[0]), be.n_hidden, 2
+    z = lambda *s: torch.zeros(*s, device=cuda)  # noqa: E731
+    ph = torch.zeros(R, NH, dtype=torch.int8, device=cuda)
+    args = (z(R, n0), z(R, n0) + 1, [1], z(R, 1), z(R, 1) + 1, z(R, NH) - 1, z(R, NH) + 1, z(R, NH) - 1,
+            z(R, NH) + 1, ph, ph, z(R, NH), z(R, NH), z(R, NH), z(R, NH), z(R) + 0.5)
+    with pytest.raises(RuntimeError):
+        hip.beta_level(be, *args, iters=2, batched=True, **LR)
+    with pytest.raises(RuntimeError):
+        hip.beta_opt16(be, *args, 2, LR["lr_a"], LR["lr_b"], LR["lr_t"])
