@@ -23,14 +23,10 @@
 #include <stdexcept>
 #include <vector>
 
-#include "args.h"
-#include "devmem.h"
-#include "exact_host.h"
+#include "runtime_host.h"
 
 namespace py = pybind11;
 
-extern "C" int fa_bounds_launch(const NetDesc& net, BoundArgs args, hipStream_t stream);
-extern "C" int fa_point_try_launch(const NetDesc& net, BoundArgs a, hipStream_t stream);
 extern "C" int fa_refine_launch(const NetDesc& net, BoundArgs a, hipStream_t stream);
 extern "C" int fa_beta_launch(const NetDesc& nd, BetaArgs a, hipStream_t stream);
 extern "C" int fa_beta_opt16_fits(const NetDesc& nd);
@@ -50,12 +46,8 @@ const NetDesc& fa_net_desc(py::handle net);
 
 namespace {
 
-void bck(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-void bckl(int rc, const char* what) {
-  if (rc != 0) throw std::runtime_error(std::string(what) + " launch failed, code " + std::to_string(rc));
-}
+using fa_rt::ck;
+using fa_rt::ckl;
 
 template <typename T>
 using BBuf = fa_mem::DevBuf<T>;
@@ -73,9 +65,10 @@ struct Pool {
 class BetaRuntime {
  public:
   BetaRuntime(py::handle net, uintptr_t flat, uintptr_t wt, std::vector<int> pa, std::vector<int> ra, double tau,
-              int capacity, int batch_nodes)
-      : net_(fa_net_desc(net)), flat_((const float*)flat), wt_((const float*)wt), pa_(std::move(pa)),
-        ra_(std::move(ra)), tau_((float)tau), cap_(capacity), batch_(batch_nodes) {
+              int capacity, int batch_nodes, py::object keep)
+      : net_(fa_net_desc(net)), flat_((const float*)flat), wt_((const float*)wt), keep_(std::move(keep)),
+        pa_(std::move(pa)), ra_(std::move(ra)), tau_((float)tau), cap_(capacity), batch_(batch_nodes),
+        sink_(net_.dims[0]) {
     n0_ = net_.dims[0];
     nh_ = net_.n_hidden;
     nn_ = net_.n_neurons;
@@ -96,30 +89,11 @@ class BetaRuntime {
     skip_.ensure(B); scratch_.ensure(B * 16 * nh_); bound_.ensure(B); split_.ensure(B);
     xstar_.ensure(B * n0_); xpstar_.ensure(B * n0_); binit_.ensure(2 * B);
     rlo_.ensure(2 * B * n0_); rhi_.ensure(2 * B * n0_); rpart_.ensure(2 * B);
-    olb_.ensure(2 * B); oub_.ensure(2 * B); infeas_.ensure(2 * B);
-    Lc_.ensure(2 * B * n0_); Uc_.ensure(2 * B * n0_); L0_.ensure(2 * B); Le_.ensure(2 * B); U0_.ensure(2 * B);
-    Ue_.ensure(2 * B);
-    lay_lb_.ensure(2 * B * nn_); lay_ub_.ensure(2 * B * nn_);
+    infeas_.ensure(2 * B);
+    form_.ensure(2 * B, n0_, nn_, true);
     cpts_.ensure(2 * B * n0_); pe_lb_.ensure(2 * B); pe_ub_.ensure(2 * B);
     counters_.ensure(8);
-    hcount_buf_.ensure(4 * sizeof(int));
-    hcount_ = reinterpret_cast<int*>(hcount_buf_.p);
-    // fp64 host copy of the network for the exact confirmation
-    int np_ = 0;
-    for (int l = 0; l < net_.n_layers; ++l) np_ = std::max(np_, net_.b_off[l] + net_.dims[l + 1]);
-    std::vector<float> hf(np_);
-    bck(hipMemcpy(hf.data(), flat_, np_ * sizeof(float), hipMemcpyDeviceToHost), "cp weights");
-    exact_.n0 = n0_;
-    exact_.n_layers = net_.n_layers;
-    exact_.dims.assign(net_.dims, net_.dims + net_.n_layers + 1);
-    exact_.w_off.assign(net_.w_off, net_.w_off + net_.n_layers);
-    exact_.b_off.assign(net_.b_off, net_.b_off + net_.n_layers);
-    exact_.w.assign(hf.begin(), hf.end());
-    exact_.is_pa.assign(n0_, 0);
-    exact_.is_ra.assign(n0_, 0);
-    for (int k : pa_) exact_.is_pa[k] = 1;
-    for (int k : ra_) exact_.is_ra[k] = 1;
-    exact_.tau = tau_;
+    exact_ = fa_rt::make_exact(net_, flat_, pa_, ra_, tau_);   // ra_ is empty unless relaxed
   }
 
   // roots: device pointers of R0 root nodes in the pool layout (part, osg, lo, hi, plo, phi, va, vb,
@@ -159,8 +133,6 @@ class BetaRuntime {
       pgsum_.ensure(B * 4 * nh_);
       pgn_.ensure(B);
     }
-    box_lo_ = box_lo.data();
-    box_hi_ = box_hi.data();
     status_.ensure(P); nodes_.ensure(P); probed_.ensure(P); part_closed_.ensure(P);
     tree_cnt_.ensure(std::max(R0, 1)); tree_done_.ensure(std::max(R0, 1)); tree_part_.ensure(std::max(R0, 1));
     ensure_pool(0, std::max(R0, 1));
@@ -177,21 +149,21 @@ class BetaRuntime {
     int* tid = reinterpret_cast<int*>(hstage_.p + o_ti);
     for (int k = 0; k < R0; ++k) tid[k] = k;
     stage_.ensure(sb);
-    bck(hipMemcpyAsync(stage_.p, hstage_.p, sb, hipMemcpyHostToDevice, st), "cp stage");
-    bck(hipMemcpyAsync(status_.p, stage_.p, P, hipMemcpyDeviceToDevice, st), "cp status");
-    bck(hipMemcpyAsync(tree_part_.p, stage_.p + ((P + 3) & ~3), (size_t)R0 * sizeof(int), hipMemcpyDeviceToDevice,
+    ck(hipMemcpyAsync(stage_.p, hstage_.p, sb, hipMemcpyHostToDevice, st), "cp stage");
+    ck(hipMemcpyAsync(status_.p, stage_.p, P, hipMemcpyDeviceToDevice, st), "cp status");
+    ck(hipMemcpyAsync(tree_part_.p, stage_.p + ((P + 3) & ~3), (size_t)R0 * sizeof(int), hipMemcpyDeviceToDevice,
                        st), "cp tree_part");
-    bck(hipMemsetAsync(nodes_.p, 0, P * sizeof(int), st), "memset nodes");
-    bck(hipMemsetAsync(probed_.p, 0, P, st), "memset probed");
-    bck(hipMemcpyAsync(part_closed_.p, stage_.p + o_c0, (size_t)P * sizeof(int), hipMemcpyDeviceToDevice, st),
+    ck(hipMemsetAsync(nodes_.p, 0, P * sizeof(int), st), "memset nodes");
+    ck(hipMemsetAsync(probed_.p, 0, P, st), "memset probed");
+    ck(hipMemcpyAsync(part_closed_.p, stage_.p + o_c0, (size_t)P * sizeof(int), hipMemcpyDeviceToDevice, st),
         "cp closed0");
-    bck(hipMemsetAsync(tree_done_.p, 0, std::max(R0, 1), st), "memset tree_done");
-    bck(hipMemsetAsync(counters_.p, 0, 8 * sizeof(int), st), "memset counters");   // [2]: probe stops
+    ck(hipMemsetAsync(tree_done_.p, 0, std::max(R0, 1), st), "memset tree_done");
+    ck(hipMemsetAsync(counters_.p, 0, 8 * sizeof(int), st), "memset counters");   // [2]: probe stops
     copy_roots(roots, R0, st);
-    bck(hipMemcpyAsync(pool_[0].tree.p, stage_.p + o_ti, (size_t)R0 * sizeof(int), hipMemcpyDeviceToDevice, st),
+    ck(hipMemcpyAsync(pool_[0].tree.p, stage_.p + o_ti, (size_t)R0 * sizeof(int), hipMemcpyDeviceToDevice, st),
         "root tree ids");
-    std::vector<int64_t> cex_x((size_t)P * n0_, 0), cex_xp((size_t)P * n0_, 0);
-    std::vector<char> got(P, 0);
+    fa_exact::Witnesses wit(P, n0_, box_lo.data(), box_hi.data());
+    hcount_.reset();
     int cur = 0;
     long long n_in = R0;
     int levels = 0;
@@ -207,14 +179,14 @@ class BetaRuntime {
         }
         const int nxt = cur ^ 1;
         ensure_pool(nxt, (int)std::min<long long>(2 * n_in, cap_));
-        ensure_cand(n_in);
-        bck(hipMemsetAsync(counters_.p, 0, 2 * sizeof(int), st), "reset counters");
-        bck(hipMemsetAsync(tree_cnt_.p, 0, std::max(R0, 1) * sizeof(int), st), "reset tree counts");
+        sink_.ensure_cand(n_in, 1 << 14);
+        ck(hipMemsetAsync(counters_.p, 0, 2 * sizeof(int), st), "reset counters");
+        ck(hipMemsetAsync(tree_cnt_.p, 0, std::max(R0, 1) * sizeof(int), st), "reset tree counts");
         // the level's nodes per partition first (the budget test of every sub-batch sees the whole level)
         for (long long s = 0; s < n_in; s += batch_) {
           BetaPoolArgs c = pool_args(cur, nxt, s, (int)std::min<long long>(batch_, n_in - s), P, budget, warm_beta);
           c.count = 1;
-          bckl(fa_bb_count_launch(c, st), "beta count");
+          ckl(fa_bb_count_launch(c, st), "beta count");
         }
         const bool root = levels == 0;
         const float sc = root ? 1.f : child_lr;
@@ -222,23 +194,24 @@ class BetaRuntime {
           const int nb = (int)std::min<long long>(batch_, n_in - s);
           BetaPoolArgs a = pool_args(cur, nxt, s, nb, P, budget, warm_beta);
           a.root = root ? 1 : 0;
-          bckl(fa_bb_count_launch(a, st), "beta skip");          // a.count = 0: this slice's skip flags
+          ckl(fa_bb_count_launch(a, st), "beta skip");          // a.count = 0: this slice's skip flags
           if (!root && tighten) tighten_slice(a, st);
           bound_slice(a, cur, s, nb, root ? root_iters : iters, lr_a * sc, lr_b * sc, lr_t * sc, decay, lookahead,
                       beta_pos, stall, pgap, st, root ? 0 : feas_iters, lr_a, lr_b, lr_t);
-          bckl(fa_bb_cand_launch(a, st), "beta cand");
-          screen_slice(nb, st);
-          bckl(fa_bb_split_launch(a, st), "beta split");
+          ckl(fa_bb_cand_launch(a, st), "beta cand");
+          fa_rt::screen_points(net_, flat_, cpts_.p, 2 * nb, pe_lb_.p, pe_ub_.p, st);
+          ckl(fa_bb_split_launch(a, st), "beta split");
         }
-        bckl(fa_bb_settle_launch(R0, tree_cnt_.p, tree_done_.p, tree_part_.p, part_closed_.p, P, status_.p,
-                                 nodes_.p, probe_at, probed_.p, counters_.p + 2, counters_.p, hcount_, st),
+        ckl(fa_bb_settle_launch(R0, tree_cnt_.p, tree_done_.p, tree_part_.p, part_closed_.p, P, status_.p,
+                                 nodes_.p, probe_at, probed_.p, counters_.p + 2, counters_.p, hcount_.host_ptr(),
+                                 st),
              "beta settle");
-        bck(hipStreamSynchronize(st), "sync");
+        ck(hipStreamSynchronize(st), "sync");
         total += n_in;
         ++levels;
-        const int n_out = std::min((int)((volatile int*)hcount_)[0], pool_[nxt].cap);
-        const int n_cand = std::min((int)((volatile int*)hcount_)[1], cand_alloc_);
-        if (n_cand > 0) confirm_candidates(n_cand, confirm, got, cex_x, cex_xp, st);
+        const int n_out = std::min(hcount_.children(), pool_[nxt].cap);
+        const int n_cand = std::min(hcount_.candidates(), sink_.cand_alloc_);
+        if (n_cand > 0) sink_.confirm_candidates(n_cand, wit, &exact_, confirm, status_.p, st);
         cur = nxt;
         n_in = n_out;
       }
@@ -247,16 +220,16 @@ class BetaRuntime {
     const size_t hn_off = ((size_t)P + 15) & ~size_t(15);
     const size_t hc_off = hn_off + (size_t)P * sizeof(int) + 32;
     hout_.ensure(hc_off + (size_t)P * sizeof(int));
-    bck(hipMemcpyAsync(hout_.p + hc_off, part_closed_.p, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, st),
+    ck(hipMemcpyAsync(hout_.p + hc_off, part_closed_.p, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, st),
         "cp closed out");
     int dev_next = 0;     // the last level's child count as the device has it (the loop saw 0)
-    bck(hipMemcpyAsync(hout_.p + hn_off + (size_t)P * sizeof(int) + 16, counters_.p, sizeof(int),
+    ck(hipMemcpyAsync(hout_.p + hn_off + (size_t)P * sizeof(int) + 16, counters_.p, sizeof(int),
                        hipMemcpyDeviceToHost, st), "cp next count");
-    bck(hipMemcpyAsync(hout_.p, status_.p, P, hipMemcpyDeviceToHost, st), "cp status out");
-    bck(hipMemcpyAsync(hout_.p + hn_off, nodes_.p, P * sizeof(int), hipMemcpyDeviceToHost, st), "cp nodes out");
-    bck(hipMemcpyAsync(hout_.p + hn_off + (size_t)P * sizeof(int), counters_.p + 2, 4 * sizeof(int),
+    ck(hipMemcpyAsync(hout_.p, status_.p, P, hipMemcpyDeviceToHost, st), "cp status out");
+    ck(hipMemcpyAsync(hout_.p + hn_off, nodes_.p, P * sizeof(int), hipMemcpyDeviceToHost, st), "cp nodes out");
+    ck(hipMemcpyAsync(hout_.p + hn_off + (size_t)P * sizeof(int), counters_.p + 2, 4 * sizeof(int),
                        hipMemcpyDeviceToHost, st), "cp probe stops");
-    bck(hipStreamSynchronize(st), "sync");
+    ck(hipStreamSynchronize(st), "sync");
     std::memcpy(&dev_next, hout_.p + hn_off + (size_t)P * sizeof(int) + 16, sizeof(int));
     const int* hclosed = reinterpret_cast<const int*>(hout_.p + hc_off);
     const int8_t* hs = reinterpret_cast<const int8_t*>(hout_.p);
@@ -269,7 +242,7 @@ class BetaRuntime {
     std::vector<char> left(P, 0);
     if (timed_out && n_in > 0) {
       std::vector<int> lp((size_t)n_in);
-      bck(hipMemcpy(lp.data(), pool_[cur].part.p, n_in * sizeof(int), hipMemcpyDeviceToHost), "cp left");
+      ck(hipMemcpy(lp.data(), pool_[cur].part.p, n_in * sizeof(int), hipMemcpyDeviceToHost), "cp left");
       for (int p : lp) left[p] = 1;
     }
     py::array_t<int8_t> status_out(P);
@@ -283,7 +256,7 @@ class BetaRuntime {
     int over = 0;
     for (int p = 0; p < P; ++p) {
       int8_t v = hs[p];
-      if (got[p]) {
+      if (wit.got[p]) {
         v = 1;
       } else if (v == 3 || v == 4) {
         if (left[p]) {
@@ -295,13 +268,13 @@ class BetaRuntime {
           ++unclosed;
         }
       }
-      if (v == 0 && status0.data()[p] == 3 && !got[p]) ++over;
+      if (v == 0 && status0.data()[p] == 3 && !wit.got[p]) ++over;
       status_out.mutable_data()[p] = v;
       nodes_out.mutable_data()[p] = hn[p];
     }
     py::array_t<int64_t> ax({P, n0_}), axp({P, n0_});
-    std::memcpy(ax.mutable_data(), cex_x.data(), sizeof(int64_t) * cex_x.size());
-    std::memcpy(axp.mutable_data(), cex_xp.data(), sizeof(int64_t) * cex_xp.size());
+    std::memcpy(ax.mutable_data(), wit.cex_x.data(), sizeof(int64_t) * wit.cex_x.size());
+    std::memcpy(axp.mutable_data(), wit.cex_xp.data(), sizeof(int64_t) * wit.cex_xp.size());
     py::dict stats;
     stats["levels"] = levels;
     stats["nodes"] = total;
@@ -341,7 +314,7 @@ class BetaRuntime {
     a.status = status_.p; a.part_nodes = nodes_.p; a.budget = budget; a.tree_cnt = tree_cnt_.p;
     a.skip = skip_.p;
     a.rlo = rlo_.p; a.rhi = rhi_.p; a.rpart = rpart_.p;
-    a.lay_lb = lay_lb_.p; a.lay_ub = lay_ub_.p; a.infeas = infeas_.p;
+    a.lay_lb = form_.lay_lb.p; a.lay_ub = form_.lay_ub.p; a.infeas = infeas_.p;
     a.bound = bound_.p; a.split = split_.p; a.xstar = xstar_.p; a.xpstar = xpstar_.p; a.binit = binit_.p;
     a.cpts = cpts_.p; a.pe_lb = pe_lb_.p; a.pe_ub = pe_ub_.p;
     a.opart = o.part.p; a.otree = o.tree.p; a.oosg = o.osg.p;
@@ -352,31 +325,30 @@ class BetaRuntime {
     a.count_out = counters_.p; a.cap = o.cap;
     a.nan_count = counters_.p + 3;
     a.diag = counters_.p + 4;
-    a.cand_buf = reinterpret_cast<float*>(cand_host_.p); a.cand_count = counters_.p + 1; a.cand_cap = cand_alloc_;
+    a.cand_buf = sink_.records(); a.cand_count = counters_.p + 1; a.cand_cap = sink_.cand_alloc_;
     return a;
   }
 
   // phase-aware bounds of the slice's nodes (both copies), intersected with the inherited ones
   void tighten_slice(const BetaPoolArgs& a, hipStream_t st) {
     const int R = 2 * a.N;
-    bckl(fa_bb_rows_launch(a, st), "beta rows");
-    bck(hipMemsetAsync(infeas_.p, 0, R, st), "memset infeas");
+    ckl(fa_bb_rows_launch(a, st), "beta rows");
+    ck(hipMemsetAsync(infeas_.p, 0, R, st), "memset infeas");
     BoundArgs b{};
     b.flat = flat_; b.lo = rlo_.p; b.hi = rhi_.p; b.R = R; b.symbolic = 1;
-    b.out_lb = olb_.p; b.out_ub = oub_.p;
-    b.Lc = Lc_.p; b.L0 = L0_.p; b.Le = Le_.p; b.Uc = Uc_.p; b.U0 = U0_.p; b.Ue = Ue_.p;
-    b.layer_lb = lay_lb_.p; b.layer_ub = lay_ub_.p;
+    form_.fill(b);
+    b.layer_lb = form_.lay_lb.p; b.layer_ub = form_.lay_ub.p;
     b.V = 0;
     b.skip_status = status_.p; b.skip_part = rpart_.p;
     b.phase_in = a.ph;             // node-major [n][2][nh] = row-major [2n + copy][nh]
     b.infeas = infeas_.p;
-    bckl(fa_bounds_launch(net_, b, st), "beta tighten bounds");
+    ckl(fa_bounds_launch(net_, b, st), "beta tighten bounds");
     if (refine_ok_) {
       const int rc = fa_refine_launch(net_, b, st);
       if (rc == -1) refine_ok_ = false;
-      else bckl(rc, "beta tighten refine");
+      else ckl(rc, "beta tighten refine");
     }
-    bckl(fa_bb_intersect_launch(a, st), "beta intersect");
+    ckl(fa_bb_intersect_launch(a, st), "beta intersect");
   }
 
   void bound_slice(const BetaPoolArgs& pa, int cur, long long s, int nb, int iters, float lr_a, float lr_b,
@@ -434,23 +406,14 @@ class BetaRuntime {
     }
   }
 
-  void screen_slice(int nb, hipStream_t st) {
-    BoundArgs pb{};
-    pb.flat = flat_; pb.lo = cpts_.p; pb.hi = cpts_.p; pb.R = 2 * nb; pb.symbolic = 0;
-    pb.out_lb = pe_lb_.p; pb.out_ub = pe_ub_.p;
-    const int prc = fa_point_try_launch(net_, pb, st);
-    if (prc < 0) bckl(-prc, "beta points");
-    if (prc == 0) bckl(fa_bounds_launch(net_, pb, st), "beta points (bounds)");
-  }
-
   void copy_roots(const std::vector<uintptr_t>& r, int R0, hipStream_t st) {
     Pool& p = pool_[0];
     auto cp = [&](void* dst, uintptr_t src, size_t bytes, const char* what) {
       if (!src) {
-        bck(hipMemsetAsync(dst, 0, bytes, st), what);
+        ck(hipMemsetAsync(dst, 0, bytes, st), what);
         return;
       }
-      bck(hipMemcpyAsync(dst, (const void*)src, bytes, hipMemcpyDeviceToDevice, st), what);
+      ck(hipMemcpyAsync(dst, (const void*)src, bytes, hipMemcpyDeviceToDevice, st), what);
     };
     const size_t R = (size_t)R0;
     cp(p.part.p, r[0], R * sizeof(int), "root part");
@@ -477,9 +440,7 @@ class BetaRuntime {
     Pool& p = pool_[i];
     const int want = std::min(std::max(need, 1), cap_);
     if (want <= p.cap) return;
-    int n = std::max(p.cap, 1 << 12);
-    while (n < want) n = (n > cap_ / 2) ? cap_ : n * 2;
-    n = std::min(n, cap_);
+    const int n = fa_rt::grow_to(p.cap, want, 1 << 12, cap_);
     const size_t N = (size_t)n;
     p.part.ensure(N); p.tree.ensure(N); p.osg.ensure(N);
     p.lo.ensure(N * n0_); p.hi.ensure(N * n0_);
@@ -490,79 +451,10 @@ class BetaRuntime {
     p.cap = n;
   }
 
-  void ensure_cand(long long need) {
-    if (need <= cand_alloc_) return;
-    long long n = std::max<long long>(cand_alloc_, 1 << 14);
-    while (n < need) n *= 2;
-    n = std::min<long long>(n, 1LL << 24);
-    cand_host_.ensure((size_t)n * (2 * n0_ + 1) * sizeof(float));
-    cand_alloc_ = (int)n;
-  }
-
-  // called WITHOUT the GIL; takes it only around the Python confirmation callback
-  void confirm_candidates(int n_cand, py::object& confirm, std::vector<char>& got, std::vector<int64_t>& cex_x,
-                          std::vector<int64_t>& cex_xp, hipStream_t st) {
-    const size_t rec = (size_t)2 * n0_ + 1;
-    const float* hc = reinterpret_cast<const float*>(cand_host_.p);   // written by the split kernel
-    std::vector<float> buf((size_t)n_cand * 2 * n0_);
-    std::vector<int> parts(n_cand);
-    for (int i = 0; i < n_cand; ++i) {
-      std::memcpy(buf.data() + (size_t)i * 2 * n0_, hc + (size_t)i * rec, sizeof(float) * 2 * n0_);
-      std::memcpy(&parts[i], hc + (size_t)i * rec + 2 * n0_, sizeof(int));
-    }
-    std::vector<char> ok(n_cand, 0);
-    std::vector<int> ask;
-    for (int i = 0; i < n_cand; ++i) {
-      if (got[parts[i]]) continue;
-      const int r = exact_.check(buf.data() + (size_t)i * 2 * n0_, box_lo_ + (size_t)parts[i] * n0_,
-                                 box_hi_ + (size_t)parts[i] * n0_);
-      if (r < 0) ask.push_back(i);
-      else ok[i] = (char)r;
-    }
-    if (!ask.empty()) {
-      py::gil_scoped_acquire gil;
-      const int na = (int)ask.size();
-      py::array_t<float> abuf({na, 2 * n0_});
-      py::array_t<int> aparts(na);
-      for (int k = 0; k < na; ++k) {
-        std::memcpy(abuf.mutable_data() + (size_t)k * 2 * n0_, buf.data() + (size_t)ask[k] * 2 * n0_,
-                    sizeof(float) * 2 * n0_);
-        aparts.mutable_data()[k] = parts[ask[k]];
-      }
-      py::array_t<bool> res = confirm(aparts, abuf).cast<py::array_t<bool>>();
-      for (int k = 0; k < na; ++k) ok[ask[k]] = res.data()[k] ? 1 : 0;
-    }
-    // each partition's witness: the first confirmed pair in (partition, lexicographic pair) order
-    std::vector<int> order(n_cand);
-    for (int i = 0; i < n_cand; ++i) order[i] = i;
-    const float* Bf = buf.data();
-    const size_t w2 = (size_t)2 * n0_;
-    std::sort(order.begin(), order.end(), [&](int x, int y) {
-      if (parts[x] != parts[y]) return parts[x] < parts[y];
-      return std::lexicographical_compare(Bf + x * w2, Bf + (x + 1) * w2, Bf + y * w2, Bf + (y + 1) * w2);
-    });
-    std::vector<int> newly;
-    for (int i : order) {
-      const int p = parts[i];
-      if (!ok[i] || got[p]) continue;
-      got[p] = 1;
-      newly.push_back(p);
-      for (int d = 0; d < n0_; ++d) {
-        cex_x[(size_t)p * n0_ + d] = (int64_t)std::llround(Bf[(size_t)i * w2 + d]);
-        cex_xp[(size_t)p * n0_ + d] = (int64_t)std::llround(Bf[(size_t)i * w2 + n0_ + d]);
-      }
-    }
-    if (!newly.empty()) {
-      // SAT partitions stop: their nodes are skipped from the next level on (count kernel)
-      for (size_t k = 0; k < newly.size(); ++k)
-        bck(hipMemsetAsync(status_.p + newly[k], 1, 1, st), "set sat");
-      bck(hipStreamSynchronize(st), "sync");
-    }
-  }
-
   NetDesc net_;
   const float* flat_;
   const float* wt_;
+  py::object keep_;   // owners of the memory behind flat_ and wt_, held for the runtime's lifetime
   std::vector<int> pa_, ra_;
   float tau_ = 0.f;
   bool relaxed_ = false;
@@ -570,31 +462,29 @@ class BetaRuntime {
   int n0_ = 0, nh_ = 0, nn_ = 0, npa_ = 0;
   bool refine_ok_ = true;
   Pool pool_[2];
-  int cand_alloc_ = 0;
   fa_exact::ExactChecker exact_;
-  const float* box_lo_ = nullptr;
-  const float* box_hi_ = nullptr;
   BBuf<uint8_t> skip_, infeas_, probed_, tree_done_;
   bool batched_ = false;
   BBuf<float> pgsum_, pgn_;
-  BBuf<float> scratch_, xstar_, xpstar_, binit_, rlo_, rhi_, olb_, oub_, Lc_, Uc_, L0_, Le_, U0_, Ue_, lay_lb_,
-      lay_ub_, cpts_, pe_lb_, pe_ub_;
+  BBuf<float> scratch_, xstar_, xpstar_, binit_, rlo_, rhi_, cpts_, pe_lb_, pe_ub_;
+  fa_rt::FormBufs form_;
   BBuf<double> bound_;
   BBuf<int> split_, rpart_, counters_, nodes_, part_closed_, tree_cnt_, tree_part_;
   BBuf<int8_t> status_;
   BBuf<unsigned char> stage_;
-  fa_mem::HostBuf hcount_buf_{true};   // coherent: the settle kernel writes the level counters
-  int* hcount_ = nullptr;
-  // pinned staging (released / regrown only after the stream synchronisation that retires its copy)
+  fa_rt::LevelCounters hcount_;
+  // pinned staging under the buffer-lifetime rule of runtime_host.h (released / regrown only after
+  // the stream synchronisation that retires its copy)
   fa_mem::HostBuf hstage_, hout_;
-  fa_mem::HostBuf cand_host_{true};   // candidate records (coherent pinned, written by the split kernel)
+  fa_rt::CandSink sink_;
 };
 
 void register_beta(py::module& m) {
   py::class_<BetaRuntime>(m, "BetaRuntime")
-      .def(py::init<py::handle, uintptr_t, uintptr_t, std::vector<int>, std::vector<int>, double, int, int>(),
+      .def(py::init<py::handle, uintptr_t, uintptr_t, std::vector<int>, std::vector<int>, double, int, int,
+                    py::object>(),
            py::arg("net"), py::arg("flat"), py::arg("wt"), py::arg("pa"), py::arg("ra"), py::arg("tau"),
-           py::arg("capacity"), py::arg("batch_nodes"))
+           py::arg("capacity"), py::arg("batch_nodes"), py::arg("keep") = py::none())
       .def("solve", &BetaRuntime::solve, py::arg("roots"), py::arg("R0"), py::arg("status"), py::arg("tree_part"),
            py::arg("box_lo"), py::arg("box_hi"), py::arg("budget"), py::arg("probe_at"), py::arg("time_budget"),
            py::arg("cfg"), py::arg("confirm"), py::arg("stream"), py::arg("closed0"));

@@ -13,8 +13,7 @@
 #include <stdexcept>
 #include <vector>
 
-#include "args.h"
-#include "devmem.h"
+#include "runtime_host.h"
 
 namespace py = pybind11;
 
@@ -54,10 +53,7 @@ extern "C" int fa_pack_masks_launch(const uint8_t* src, int P, int N, int stride
 template <typename T>
 static T* P(uintptr_t p) { return reinterpret_cast<T*>(p); }
 
-static float gamma_up(int k, double unit) {
-  const double ku = (k + 2) * unit;
-  return std::nextafter((float)(ku / (1.0 - ku)), INFINITY);
-}
+using fa_rt::gamma_up;
 
 struct Net {
   NetDesc d;
@@ -129,9 +125,7 @@ extern "C" int fa_backward_launch(const NetDesc& net, BoundArgs a, hipStream_t s
 extern "C" int fa_refine_crown_launch(const NetDesc& net, BoundArgs a, hipStream_t stream);
 void register_csv(py::module& m);
 
-static void check(int rc, const char* what) {
-  if (rc != 0) throw std::runtime_error(std::string(what) + " launch failed, code " + std::to_string(rc));
-}
+using fa_rt::ckl;
 
 PYBIND11_MODULE(_C, m) {
   m.doc() = "fairify_amd CDNA4 (gfx950) kernels";
@@ -169,7 +163,7 @@ PYBIND11_MODULE(_C, m) {
     a.fold = fold;
     a.phase_in = P<const int8_t>(phase_in);
     a.infeas = P<uint8_t>(infeas);
-    check(fa_bounds_launch(d, a, (hipStream_t)stream), "bounds");
+    ckl(fa_bounds_launch(d, a, (hipStream_t)stream), "bounds");
   }, py::arg("net"), py::arg("flat"), py::arg("lo"), py::arg("hi"), py::arg("dead_in"), py::arg("R"),
      py::arg("symbolic"), py::arg("out_lb"), py::arg("out_ub"), py::arg("Lc"), py::arg("L0"), py::arg("Le"),
      py::arg("Uc"), py::arg("U0"), py::arg("Ue"), py::arg("layer_lb"), py::arg("layer_ub"), py::arg("dead_out"),
@@ -219,7 +213,7 @@ PYBIND11_MODULE(_C, m) {
     a.Uc = P<float>(Uc); a.U0 = P<float>(U0); a.Ue = P<float>(Ue);
     a.layer_lb = P<float>(layer_lb);
     a.layer_ub = P<float>(layer_ub);
-    check(fa_crown_launch(net.d, a, (hipStream_t)stream), "crown");
+    ckl(fa_crown_launch(net.d, a, (hipStream_t)stream), "crown");
   });
 
   // back-substituted hidden-layer bounds (refine.hip), tightening layer_lb / layer_ub of a preceding
@@ -296,8 +290,8 @@ PYBIND11_MODULE(_C, m) {
     a.out_lb = P<float>(out_lb);
     a.out_ub = P<float>(out_ub);
     int rc = fa_point_try_launch(net.d, a, (hipStream_t)stream);
-    if (rc < 0) check(-rc, "point_bounds");
-    if (rc == 0) check(fa_bounds_launch(net.d, a, (hipStream_t)stream), "point_bounds(ibp)");
+    if (rc < 0) ckl(-rc, "point_bounds");
+    if (rc == 0) ckl(fa_bounds_launch(net.d, a, (hipStream_t)stream), "point_bounds(ibp)");
   });
 
   m.def("forward", [](const Net& net, uintptr_t flat, uintptr_t x, int B, uintptr_t dead, uintptr_t out,
@@ -308,7 +302,7 @@ PYBIND11_MODULE(_C, m) {
     a.B = B;
     a.dead = P<const uint8_t>(dead);
     a.out = P<float>(out);
-    check(fa_forward_launch(net.d, a, (hipStream_t)stream), "forward");
+    ckl(fa_forward_launch(net.d, a, (hipStream_t)stream), "forward");
   });
 
   m.def("sim", [](const Net& net, uintptr_t flat, uintptr_t lo, uintptr_t hi, uintptr_t pids, int Pn, int n_samples,
@@ -341,7 +335,7 @@ PYBIND11_MODULE(_C, m) {
     a.z0 = P<float>(z0);
     a.keys = P<int>(keys);
     a.split = split;
-    check(fa_sim_launch(net.d, a, (hipStream_t)stream), "sim");
+    ckl(fa_sim_launch(net.d, a, (hipStream_t)stream), "sim");
   });
 
   // returns false if the partition's candidate rows do not fit in LDS (caller keeps PyTorch)
@@ -370,7 +364,7 @@ PYBIND11_MODULE(_C, m) {
     a.wit_xp = P<float>(wit_xp);
     const int rc = fa_ascent_launch(net.d, a, (hipStream_t)stream);
     if (rc == -1) return false;
-    check(rc, "ascent");
+    ckl(rc, "ascent");
     return true;
   });
 
@@ -408,13 +402,13 @@ PYBIND11_MODULE(_C, m) {
     a.dseed = dseed;
     const int rc = fa_falsify_launch(net.d, a, (hipStream_t)stream);
     if (rc == 0) return false;
-    if (rc < 0) check(-rc, "falsify");
+    if (rc < 0) ckl(-rc, "falsify");
     return true;
   });
 
   m.def("prune_masks", [](const Net& net, int Pn, uintptr_t counts, uintptr_t ub, int ub_stride, uintptr_t sym_dead,
                           uintptr_t code, uintptr_t cnt, uintptr_t stream) {
-    check(fa_prune_masks_launch(net.d, Pn, P<const int>(counts), P<const float>(ub), ub_stride,
+    ckl(fa_prune_masks_launch(net.d, Pn, P<const int>(counts), P<const float>(ub), ub_stride,
                                 P<const uint8_t>(sym_dead), P<uint8_t>(code), P<int>(cnt), (hipStream_t)stream),
           "prune_masks");
   });
@@ -422,7 +416,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("heuristic", [](const Net& net, int Pu, uintptr_t rows, uintptr_t lb, uintptr_t ub, int stride, uintptr_t code,
                         double q50, double qlo, double qhi, uintptr_t hnew, uintptr_t hmerged, uintptr_t hcnt,
                         uintptr_t stream) {
-    check(fa_heuristic_launch(net.d, Pu, P<const int64_t>(rows), P<const float>(lb), P<const float>(ub), stride,
+    ckl(fa_heuristic_launch(net.d, Pu, P<const int64_t>(rows), P<const float>(lb), P<const float>(ub), stride,
                               P<const uint8_t>(code), q50, qlo, qhi, P<uint8_t>(hnew), P<uint8_t>(hmerged),
                               P<int>(hcnt), (hipStream_t)stream),
           "heuristic");
@@ -435,7 +429,7 @@ PYBIND11_MODULE(_C, m) {
                                    P<const float>(hi), P<const int64_t>(pids), P<const uint8_t>(dead), S, seed,
                                    P<int>(agree), (hipStream_t)stream);
     if (rc == 0) return false;
-    if (rc < 0) check(-rc, "agree");
+    if (rc < 0) ckl(-rc, "agree");
     return true;
   });
 
@@ -472,7 +466,7 @@ PYBIND11_MODULE(_C, m) {
     a.cand_x = P<float>(cand_x); a.cand_xp = P<float>(cand_xp);
     a.cand_v = P<int64_t>(cand_v); a.cand_o = P<int64_t>(cand_o);
     a.scores = P<float>(scores); a.leaf = P<uint8_t>(leaf);
-    check(fa_certify_launch(a, (hipStream_t)stream), "certify");
+    ckl(fa_certify_launch(a, (hipStream_t)stream), "certify");
   });
 
   m.def("decode", [](std::vector<int> radix, std::vector<long long> div, std::vector<int> chunk_off,
@@ -492,27 +486,27 @@ PYBIND11_MODULE(_C, m) {
       d.base_lo[k] = base_lo[k];
       d.base_hi[k] = base_hi[k];
     }
-    check(fa_decode_launch(d, P<const int64_t>(ids), Pn, P<const float>(chunk_lo), P<const float>(chunk_hi),
+    ckl(fa_decode_launch(d, P<const int64_t>(ids), Pn, P<const float>(chunk_lo), P<const float>(chunk_hi),
                            P<float>(lo), P<float>(hi), (hipStream_t)stream),
           "decode");
   });
   m.def("pack_masks", [](uintptr_t src, int Pn, int N, int stride, int sel, uintptr_t out, int NB, uintptr_t hash,
                          uintptr_t stream) {
-    check(fa_pack_masks_launch(P<const uint8_t>(src), Pn, N, stride, sel, P<uint8_t>(out), NB,
+    ckl(fa_pack_masks_launch(P<const uint8_t>(src), Pn, N, stride, sel, P<uint8_t>(out), NB,
                                P<unsigned long long>(hash), (hipStream_t)stream),
           "pack_masks");
   });
   m.def("knn", [](uintptr_t X, int n, int d, int k, uintptr_t idx, uintptr_t dist, uintptr_t stream) {
-    check(fa_knn_launch(P<const float>(X), n, d, k, P<int>(idx), P<float>(dist), (hipStream_t)stream), "knn");
+    ckl(fa_knn_launch(P<const float>(X), n, d, k, P<int>(idx), P<float>(dist), (hipStream_t)stream), "knn");
   });
   m.def("actdiff", [](const Net& net, uintptr_t flat, uintptr_t x, uintptr_t xp, int npairs, uintptr_t sum_out,
                       uintptr_t stream) {
-    check(fa_actdiff_launch(net.d, P<const float>(flat), P<const float>(x), P<const float>(xp), npairs,
+    ckl(fa_actdiff_launch(net.d, P<const float>(flat), P<const float>(x), P<const float>(xp), npairs,
                             P<float>(sum_out), (hipStream_t)stream),
           "actdiff");
   });
   m.def("trace_marker", [](int tag, uintptr_t sink, uintptr_t stream) {
-    check(fa_trace_marker_launch(tag, P<int>(sink), (hipStream_t)stream), "trace_marker");
+    ckl(fa_trace_marker_launch(tag, P<int>(sink), (hipStream_t)stream), "trace_marker");
   });
   // the arguments of one beta level (beta_level and the batched entry points share them)
   auto beta_args = [](const Net& net, uintptr_t flat, uintptr_t wt, int R, const std::vector<int>& pa, uintptr_t lo,

@@ -5,15 +5,19 @@
 // (x, x') that agrees on the non-protected features, differs on a protected one, stays in the
 // partition box, and gets different predictions (src/AC/Verify-AC.py:127-163).
 //
-// Pure host code shared by the BaB runtime (csrc/bab_runtime.cpp, 8 host threads, no GIL) and
+// Pure host code shared by the native runtimes (csrc/runtime_host.h, 8 host threads, no GIL) and
 // the host sanitizer harness (tools/exact_tsan.cpp, -fsanitize=thread / address,undefined):
 // every method is const and touches only the checker's immutable tables and the caller's
-// buffers, so one checker may serve any number of threads.
+// buffers, so one checker may serve any number of threads.  select_witnesses (below) turns a
+// level's candidate records into each partition's witness, on the caller's per-solve state.
 #pragma once
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
 namespace fa_exact {
@@ -104,5 +108,77 @@ struct ExactChecker {
     return sx * sp < 0 ? 1 : 0;
   }
 };
+
+// Verdict state of one solve's P partitions: their boxes (borrowed, [P][n0]) and the witnesses
+// confirmed so far.  A partition in `got` is SAT and its witness is final.
+struct Witnesses {
+  int P, n0;
+  const float* box_lo;
+  const float* box_hi;
+  std::vector<char> got;
+  std::vector<int64_t> cex_x, cex_xp;   // [P][n0], rounded to integers
+  Witnesses(int P_, int n0_, const float* lo, const float* hi)
+      : P(P_), n0(n0_), box_lo(lo), box_hi(hi), got(P_, 0), cex_x((size_t)P_ * n0_, 0), cex_xp((size_t)P_ * n0_, 0) {}
+};
+
+// One BaB level's candidate records -> the partitions they newly prove SAT (the single
+// implementation behind the three runtimes' confirm_candidates; csrc/runtime_host.h).
+// rec: n_cand records of 2 n0 + 1 floats, x | x' | partition id (int bits), in the device's atomic
+// append order.  Candidates of partitions already in w.got are dropped first (the selection
+// below would ignore them anyway).  The others are decided by chk->check; what it leaves open
+// (-1), or every one when chk is null (native exact check off), goes to
+//   ask(slots, pairs [n][2 n0], partition ids) -> one bool each.
+// Each partition's witness is the first confirmed pair in (partition, lexicographic pair) order, so
+// it depends neither on the append order nor on which partitions share the level.  A partition
+// id outside [0, P) throws before anything is indexed with it.
+template <typename Ask>
+std::vector<int> select_witnesses(const float* rec, int n_cand, Witnesses& w, const ExactChecker* chk, Ask&& ask) {
+  const int n0 = w.n0;
+  const size_t w2 = (size_t)2 * n0, rw = w2 + 1;
+  std::vector<int> parts(n_cand);
+  for (int i = 0; i < n_cand; ++i) {
+    std::memcpy(&parts[i], rec + (size_t)i * rw + w2, sizeof(int));
+    if (parts[i] < 0 || parts[i] >= w.P)
+      throw std::runtime_error("candidate record in slot " + std::to_string(i) + ": partition id " +
+                               std::to_string(parts[i]) + " outside [0, " + std::to_string(w.P) + ")");
+  }
+  std::vector<char> ok(n_cand, 0);
+  std::vector<int> order, slots;   // candidates of undecided partitions; those of them to ask about
+  for (int i = 0; i < n_cand; ++i) {
+    const int p = parts[i];
+    if (w.got[p]) continue;
+    order.push_back(i);
+    const int r = chk ? chk->check(rec + (size_t)i * rw, w.box_lo + (size_t)p * n0, w.box_hi + (size_t)p * n0) : -1;
+    if (r < 0) slots.push_back(i);
+    else ok[i] = (char)r;
+  }
+  if (!slots.empty()) {
+    std::vector<float> pairs(slots.size() * w2);
+    std::vector<int> aparts(slots.size());
+    for (size_t k = 0; k < slots.size(); ++k) {
+      std::memcpy(pairs.data() + k * w2, rec + (size_t)slots[k] * rw, sizeof(float) * w2);
+      aparts[k] = parts[slots[k]];
+    }
+    const std::vector<char> res = ask(slots, pairs, aparts);
+    if (res.size() != slots.size()) throw std::runtime_error("candidate confirmation: answer count mismatch");
+    for (size_t k = 0; k < slots.size(); ++k) ok[slots[k]] = res[k] ? 1 : 0;
+  }
+  std::sort(order.begin(), order.end(), [&](int x, int y) {
+    if (parts[x] != parts[y]) return parts[x] < parts[y];
+    return std::lexicographical_compare(rec + x * rw, rec + x * rw + w2, rec + y * rw, rec + y * rw + w2);
+  });
+  std::vector<int> newly;
+  for (int i : order) {
+    const int p = parts[i];
+    if (!ok[i] || w.got[p]) continue;
+    w.got[p] = 1;
+    newly.push_back(p);
+    for (int d = 0; d < n0; ++d) {
+      w.cex_x[(size_t)p * n0 + d] = (int64_t)std::llround(rec[(size_t)i * rw + d]);
+      w.cex_xp[(size_t)p * n0 + d] = (int64_t)std::llround(rec[(size_t)i * rw + n0 + d]);
+    }
+  }
+  return newly;
+}
 
 }  // namespace fa_exact

@@ -408,29 +408,18 @@ class BaBSolver:
                                     pairs_np.astype(np.int64).reshape(-1).tolist(),
                                     list(self.q.ra_idx) if self.relaxed else [], float(self.q.tau),
                                     shared.tolist(), int(cap), int(self.cfg.batch_nodes), int(self.cfg.cand_cap),
-                                    float(self.be.unit), bool(self.cfg.crown), int(self.cfg.split_target), rf, sm)
+                                    float(self.be.unit), bool(self.cfg.crown), int(self.cfg.split_target), rf, sm,
+                                    self.be.flat)
 
         return checkout(self.be, "_bab_rt", key, max(self.cfg.max_pool, n_run), make)
 
     def _solve_native(self, lo_np, hi_np, status, values_np, pairs_np, mlp_exact, exact_models, t0) -> BaBResult:
         n_run = int((status == RUNNING).sum())
-        q = self.q
+        check = exact.make_confirm(mlp_exact, lo_np, hi_np, self.q, exact_models)
 
         def confirm(parts: np.ndarray, buf: np.ndarray) -> np.ndarray:
             with self.tm("bab.confirm"):
-                n = q.n
-                X = np.rint(buf[:, :n]).astype(np.int64)
-                XP = np.rint(buf[:, n:]).astype(np.int64)
-                ok = exact.check_pair_constraints(X, XP, lo_np[parts], hi_np[parts], q.pa_idx, q.ra_idx, q.tau)
-                out = np.zeros(len(parts), dtype=bool)
-                if exact_models is None:
-                    idx = np.nonzero(ok)[0]
-                    if idx.size:
-                        out[idx] = exact.is_violation(mlp_exact, X[idx], XP[idx])
-                else:
-                    for k in np.nonzero(ok)[0]:
-                        out[k] = exact.is_violation(exact_models[int(parts[k])], X[k:k + 1], XP[k:k + 1])[0]
-                return out
+                return check(parts, buf)
 
         dead_ptr = 0
         if self.dead is not None:

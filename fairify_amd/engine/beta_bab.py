@@ -457,23 +457,15 @@ class BetaBaBSolver:
                 "tighten": int(bool(cfg.tighten)), "feas_iters": int(cfg.feas_iters),
                 "batched": int(self._batched())}
 
-        def confirm(parts: np.ndarray, buf: np.ndarray) -> np.ndarray:
-            X = np.rint(buf[:, :n0]).astype(np.int64)
-            XP = np.rint(buf[:, n0:]).astype(np.int64)
-            ok = exact.check_pair_constraints(X, XP, lo_np[parts], hi_np[parts], q.pa_idx, q.ra_idx, q.tau)
-            out = np.zeros(len(parts), dtype=bool)
-            idx = np.nonzero(ok)[0]
-            if idx.size:
-                out[idx] = exact.is_violation(mlp_exact, X[idx], XP[idx])
-            return out
-
+        confirm = exact.make_confirm(mlp_exact, lo_np, hi_np, q)
         cap = int(max(cfg.max_pool, 2 * R0))
         batch = int(min(cfg.batch_nodes, 32768))
         key = (tuple(q.pa_idx), tuple(ra), tau, batch)
 
         def make(c):
-            return ext().BetaRuntime(_net(be), be.flat.data_ptr(), _beta_wt(be).data_ptr(), list(q.pa_idx), ra, tau,
-                                     int(c), batch)
+            wt = _beta_wt(be)
+            return ext().BetaRuntime(_net(be), be.flat.data_ptr(), wt.data_ptr(), list(q.pa_idx), ra, tau, int(c),
+                                     batch, (be.flat, wt))
 
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         with self.tm("beta.native"), checkout(be, "_beta_rt", key, cap, make) as rt:

@@ -112,3 +112,27 @@ def check_pair_constraints(x: np.ndarray, xp: np.ndarray, lo: np.ndarray, hi: np
     if ra:
         ok &= np.all(np.abs(x[:, ra] - xp[:, ra]) <= tau, axis=1)
     return ok
+
+
+def make_confirm(mlp_exact: MLP, lo_np: np.ndarray, hi_np: np.ndarray, q, exact_models=None):
+    """The exact confirmation callback of the native runtimes (csrc/runtime_host.h):
+    ``confirm(parts, buf)`` takes candidate pairs ``buf`` [n, 2 n0] (x | x', floats at integer
+    points) and their partition ids and returns one bool each -- the pair meets the query's
+    pre-condition in its partition's box and violates the post-condition on the exact network
+    (``exact_models[partition]`` where per-partition masked networks are given)."""
+    n0 = lo_np.shape[1]
+
+    def confirm(parts: np.ndarray, buf: np.ndarray) -> np.ndarray:
+        X = np.rint(buf[:, :n0]).astype(np.int64)
+        XP = np.rint(buf[:, n0:]).astype(np.int64)
+        ok = check_pair_constraints(X, XP, lo_np[parts], hi_np[parts], q.pa_idx, q.ra_idx, q.tau)
+        out = np.zeros(len(parts), dtype=bool)
+        idx = np.nonzero(ok)[0]
+        if exact_models is not None:
+            for k in idx:
+                out[k] = is_violation(exact_models[int(parts[k])], X[k:k + 1], XP[k:k + 1])[0]
+        elif idx.size:
+            out[idx] = is_violation(mlp_exact, X[idx], XP[idx])
+        return out
+
+    return confirm

@@ -468,7 +468,7 @@ class ReluBaBSolver:
             return ext().ReluRuntime(_net(self.be), self.be.flat.data_ptr(), list(self.q.pa_idx),
                                      values_np.astype(np.float32).reshape(-1).tolist(),
                                      pairs_np.astype(np.int64).reshape(-1).tolist(), int(cap),
-                                     int(self.cfg.batch_nodes), float(self.be.unit), rf, ra, tau, no)
+                                     int(self.cfg.batch_nodes), float(self.be.unit), rf, ra, tau, no, self.be.flat)
 
         return checkout(self.be, "_relu_rt", key, max(self.cfg.max_pool, 2 * n_root), make)
 
@@ -489,18 +489,7 @@ class ReluBaBSolver:
             status = status.copy()
             status[status == RUNNING] = UNSAT
             return status, np.zeros((P, n0), np.int64), np.zeros((P, n0), np.int64), np.zeros(P, np.int64)
-        q = self.q
-
-        def confirm(parts: np.ndarray, buf: np.ndarray) -> np.ndarray:
-            X = np.rint(buf[:, :n0]).astype(np.int64)
-            XP = np.rint(buf[:, n0:]).astype(np.int64)
-            ok = exact.check_pair_constraints(X, XP, lo_np[parts], hi_np[parts], q.pa_idx, q.ra_idx, q.tau)
-            out = np.zeros(len(parts), dtype=bool)
-            idx = np.nonzero(ok)[0]
-            if idx.size:
-                out[idx] = exact.is_violation(mlp_exact, X[idx], XP[idx])
-            return out
-
+        confirm = exact.make_confirm(mlp_exact, lo_np, hi_np, self.q)
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         with self.tm("relu.native"), self._runtime(values_np, pairs_np, n_root) as rt:
             st, cx, cxp, nodes, stats = rt.solve(lo_np.astype(np.float32), hi_np.astype(np.float32), status,

@@ -1,6 +1,9 @@
-"""Checkout pool of the native BaB runtimes (csrc/bab_runtime.cpp, csrc/relu_runtime.cpp).
+"""Checkout pool of the native BaB runtimes (csrc/bab_runtime.cpp, csrc/relu_runtime.cpp,
+csrc/beta_runtime.cpp; their shared host layer is csrc/runtime_host.h).
 
-A runtime owns device work buffers and pinned staging sized for its node capacity; one solve at
+A runtime owns device work buffers and pinned staging sized for its node capacity, and holds a
+reference (its ``keep`` argument) to the backend tensors it points into -- the flat weights, the
+beta runtime's transposed weights -- so a pooled runtime never outlives them; one solve at
 a time may use it, on any stream (every solve ends with a synchronisation of that stream, so the
 next user -- another host thread, another stream -- finds it idle).  Round 2 kept one runtime per
 (query, host thread): with 8 host threads and items moving between threads from step to step,

@@ -127,6 +127,33 @@ def test_native_relu_bab_matches_bruteforce(cuda, name, seed, bias):
             assert not v, k
 
 
+def test_native_relu_sat_flags_repeatable_without_driver_frees(cuda):
+    """Confirmed partitions are flagged SAT on the device by the shared candidate sink
+    (csrc/runtime_host.h: one staged copy + fa_set_status, no extra synchronisation).  Two solves of
+    the same boxes on one backend (the second on the pooled runtime) give the same verdicts and
+    witnesses, and the second returns no buffer to the driver."""
+    from fairify_amd.ops import ext
+
+    pre = presets.get("src/AC-sex")
+    grid, q = pre.grid(), pre.resolved()
+    m = get_model("AC-8", weights="random", seed=1)
+    ids = processing_order(grid, 0)[:64]
+    lo, hi = grid.decode(ids)
+    hi = np.minimum(hi, lo + 1)
+    be = Backend(m, cuda)
+    a = ReluBaBSolver(be, q, ReluConfig(node_budget=4096)).solve(lo, hi, m)
+    frees = ext().mem_stats()["driver_frees"]
+    b = ReluBaBSolver(be, q, ReluConfig(node_budget=4096)).solve(lo, hi, m)
+    assert ext().mem_stats()["driver_frees"] == frees
+    sat = a.status == SAT
+    assert sat.any()
+    assert np.array_equal(a.status, b.status)
+    assert np.array_equal(a.cex_x[sat], b.cex_x[sat]) and np.array_equal(a.cex_xp[sat], b.cex_xp[sat])
+    pa = q.pa_idx[0]
+    for k in np.nonzero(sat)[0]:                 # each witness is a pair of the partition's box
+        assert np.all((a.cex_x[k] >= lo[k]) & (a.cex_x[k] <= hi[k])) and a.cex_x[k][pa] != a.cex_xp[k][pa]
+
+
 @pytest.mark.parametrize("name,min_closed", [("AC-8", 20), ("AC-12", 22)])
 def test_native_relu_closes_residue(cuda, name, min_closed):
     ids = np.asarray(json.load(open(os.path.join(HERE, "data", "relu_residue.json")))[name])

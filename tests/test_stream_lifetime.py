@@ -5,7 +5,7 @@ runtime then enqueued ``hipMemcpyAsync`` from pageable ``std::vector`` temporari
 relaxed queries, rewrote a source vector in place right after enqueueing its copy (the x' boxes
 were derived from the x boxes by editing ``hl``/``hh`` between two async copies).  A pageable
 async H2D copy is staged by the HIP runtime after the call returns, so the second edit raced the
-first copy.  The rule the runtime follows now (``csrc/bab_runtime.cpp``, ``ensure_host``):
+first copy.  The rule the runtimes and their shared host layer (``csrc/runtime_host.h``) follow now:
 
 * the host side of every ``hipMemcpyAsync`` is a runtime-owned pinned buffer (``hipHostMalloc``);
 * such a buffer is only written, regrown or freed after the ``hipStreamSynchronize`` that
@@ -37,6 +37,7 @@ def _host_operands(src: str):
 
 
 RUNTIMES = ("bab_runtime.cpp", "relu_runtime.cpp", "beta_runtime.cpp")
+SHARED = "runtime_host.h"      # host layer compiled into each of them: candidate sink, level counters
 
 
 def _pinned_names(src: str):
@@ -49,10 +50,13 @@ def _pinned_names(src: str):
 
 
 def test_async_copies_use_pinned_runtime_buffers():
-    for f in RUNTIMES:
+    shared_ops = _host_operands(open(os.path.join(CSRC, SHARED)).read())
+    assert len(shared_ops) >= 1, shared_ops          # the SAT partition ids (hidx_)
+    for f in RUNTIMES + (SHARED,):
         src = open(os.path.join(CSRC, f)).read()
         ops = _host_operands(src)
-        assert len(ops) >= 3, (f, ops)
+        # a runtime's copies: its own and the ones the shared layer enqueues for it
+        assert f == SHARED or len(ops) + len(shared_ops) >= 3, (f, ops)
         pinned = _pinned_names(src)
         for kind, host in ops:
             if kind == "hipMemcpyDeviceToDevice":
@@ -74,16 +78,30 @@ def test_pinned_buffers_regrow_only_after_sync():
     cache) is preceded, within the same function, by a stream synchronisation, or sits at the
     start of a solve (the previous solve ended with a sync), or is the D2H target that the
     synchronisation right after it retires."""
-    for f in RUNTIMES:
+    for f in RUNTIMES + (SHARED,):
         src = open(os.path.join(CSRC, f)).read()
         pinned = _pinned_names(src)
-        body = src[src.index("py::tuple solve("):]
-        first_sync = body.index("hipStreamSynchronize")
+        if f == SHARED:
+            # no solve() here: every member function counts; constructors are left out as the
+            # runtimes' constructors are (they precede solve(): the object has queued nothing yet)
+            body, first_sync = src, 0
+            structs = set(re.findall(r"\nstruct (\w+) \{", src))
+            ctors = [c.start() for c in re.finditer(r"\n  (?:explicit )?(\w+)\([^)]*\)[^;{]*\{", src)
+                     if c.group(1) in structs]
+            assert {"LevelCounters", "CandSink"} <= structs and ctors
+        else:
+            body = src[src.index("py::tuple solve("):]
+            first_sync = body.index("hipStreamSynchronize")
+            ctors = []
+        seen = set()
         for m in re.finditer(r"\b(\w+)\.ensure\(", body):
             if m.group(1) not in pinned:
                 continue
             pos = m.start()
             fn_start = max(body.rfind("\n  void ", 0, pos), 0)
+            if any(fn_start < c < pos for c in ctors):
+                continue
+            seen.add(m.group(1))
             before = body[fn_start:pos]
             at_solve_start = pos < first_sync and m.group(1) == "hstage_"
             # cand_host_ (candidate records the split kernel writes into pinned memory) regrows in
@@ -95,6 +113,8 @@ def test_pinned_buffers_regrow_only_after_sync():
             assert at_solve_start or after_level_sync or "hipStreamSynchronize" in before \
                 or m.group(1) in ("hout_", "hcand_") \
                 or (m.group(1) == "cand_host_" and "void ensure_cand" in before), (f, m.group(1))
+        if f == SHARED:
+            assert seen == {"cand_host_", "hidx_"}, seen
 
 
 def test_runtime_pool_reuses_idle_runtimes():
