@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Run the fixed beta pass (engine/pipeline.py:_beta_round) repeatedly on one residue set and compare
+"""Run the fixed beta pass (engine/chunk_group.py:_beta_round) repeatedly on one residue set and compare
 verdicts and node counts run to run, under toggles (native loop / torch loop, forced weight placement,
 no tightening), to find where run-to-run differences come from.
 
@@ -31,8 +31,9 @@ def main():
     from dataclasses import replace
 
     from fairify_amd import presets
-    from fairify_amd.engine.bab import UNKNOWN
-    from fairify_amd.engine.pipeline import VerifyConfig, _beta_round, verify_chunk
+    from fairify_amd.engine.bab import UNKNOWN, pa_groups
+    from fairify_amd.engine.chunk_group import GroupState, _beta_round
+    from fairify_amd.engine.pipeline import VerifyConfig, verify_chunk
     from fairify_amd.models.zoo import get_model
     from fairify_amd.ops.backend import Backend
     from fairify_amd.partition import processing_order
@@ -54,20 +55,25 @@ def main():
     lo_np, hi_np = grid.decode(unk)
     P = unk.size
     print(f"{args.model}: {ids.size} partitions, residue {P} ({time.time() - t0:.1f}s)", flush=True)
+
+    def beta_pass(idx):
+        """The fixed beta pass on the residue rows ``idx``, from a fresh all-UNKNOWN state per PA group."""
+        status, nodes = np.full(idx.size, UNKNOWN, dtype=np.int8), np.zeros(idx.size, np.int64)
+        for g in pa_groups(q, lo_np[idx], hi_np[idx]):
+            s = GroupState(be, m, q, unk[idx[g]], lo_np[idx[g]], hi_np[idx[g]])
+            s.status[:] = UNKNOWN
+            _beta_round(s, np.arange(len(g)), cfg.beta_budget, 1e9, cfg)
+            status[g], nodes[g] = s.status, s.nodes
+        return status, nodes
+
     ref = None
     for name in args.settings.split(","):
         env = {"nat": {}, "wm0": {"FAIRIFY_BETA_WM": "0"}, "wm2": {"FAIRIFY_BETA_WM": "2"},
                "torch": {"FAIRIFY_TORCH_BETA": "1"}}[name.split("_")[0]]
         old = {k: os.environ.get(k) for k in env}
         os.environ.update(env)
-        status = np.full(P, UNKNOWN, dtype=np.int8)
-        stage = np.empty(P, dtype=object)
-        cx = np.zeros((P, lo_np.shape[1]), np.int64)
-        cxp = np.zeros_like(cx)
-        nodes = np.zeros(P, np.int64)
         t1 = time.time()
-        _beta_round(be, q, m, np.arange(P), lo_np, hi_np, cfg.beta_budget, 1e9, cfg.batch_nodes, status, stage, cx, cxp,
-                    nodes, probe_levels=cfg.beta_probe_levels, cfg=cfg)
+        status, nodes = beta_pass(np.arange(P))
         torch.cuda.synchronize()
         for k, x in old.items():
             if x is None:
@@ -90,12 +96,7 @@ def main():
         def run(k):
             idx = parts[k]
             with torch.cuda.stream(streams[k]):
-                st = np.full(idx.size, UNKNOWN, dtype=np.int8)
-                nd = np.zeros(idx.size, np.int64)
-                cx = np.zeros((idx.size, lo_np.shape[1]), np.int64)
-                _beta_round(be, q, m, np.arange(idx.size), lo_np[idx], hi_np[idx], cfg.beta_budget, 1e9,
-                            cfg.batch_nodes, st, np.empty(idx.size, dtype=object), cx, cx.copy(), nd,
-                            probe_levels=cfg.beta_probe_levels, cfg=cfg)
+                st, nd = beta_pass(idx)
                 torch.cuda.current_stream().synchronize()
             return st, nd
 
