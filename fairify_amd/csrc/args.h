@@ -449,6 +449,14 @@ struct BetaArgs {
   // instead of zero (iters = 0: the primal-gap rule sees the optimiser's averages); null: unused
   const float* pgsum;
   const float* pgn;
+  // two-phase infeasibility pass (BetaConfig.batched_feas): the feas mode of fa_beta_opt16_kernel writes
+  // the pass's best parameters to fpar [R, 4, NH] and, relaxed with the tie, its best tie multipliers to
+  // fgt [R, 2, n0] (par / t / gtie stay the main pass's: the children inherit those); fa_beta_kernel
+  // at feas = 1, iters = 0 with fpar non-null evaluates the rigorous value there (slopes clamped to
+  // [0, 1], tie multipliers to >= 0 at load: sound whatever the buffers hold).  fpar null: unused
+  float* fpar;
+  float* fgt;
+  double* fval;             // [R] optional: the infeasibility pass's rigorous value, rows that ran only
 };
 
 // Native beta-CROWN BaB level (csrc/beta_runtime.cpp, kernels csrc/beta_bab.hip): a device-resident

@@ -22,7 +22,9 @@
 // ~100 dependent passes through it, so the kernel is latency / issue bound.  The optimisation loop
 // also exists batched on MFMA, 16 nodes of one network as the 16 columns (they share W; their
 // multipliers are the B operand, the relaxation is elementwise on the accumulators):
-// csrc/beta_opt16.hip, opt-in; this kernel then runs at iters = 0 as its second phase.
+// csrc/beta_opt16.hip, opt-in; this kernel then runs at iters = 0 as its second phase.  The
+// infeasibility pass (a.feas) has the same two-phase form (BetaArgs::fpar / fgt: the proposed
+// multipliers; this kernel at feas = 1, iters = 0 decides on its rigorous value at them).
 #include <float.h>
 
 #include <algorithm>
@@ -513,13 +515,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FA_BETA_WPE
   // everywhere (lane j of its layer, j mod 64), so no lane reads a global word another lane of the
   // wave wrote (the scores and the split neuron's binit use that mapping too)
   const float* pg = (a.pgsum && a.pgn) ? a.pgsum + (size_t)r * 4 * NH : nullptr;
+  // two-phase infeasibility pass: the batched optimiser's proposals instead of the pass's own start values
+  const float* fpr = (a.feas && a.iters == 0 && a.fpar) ? a.fpar + (size_t)r * 4 * NH : nullptr;
   for (int l = 0; l < L - 1; ++l)
     for (int j = lane; j < nd.dims[l + 1]; j += 64)
       for (int q = 0; q < 4; ++q) {
         const int k = q * NH + nd.neuron_off[l] + j;
         // feas: the phase multipliers start at 0.5 on the fixed neurons (0 elsewhere), the slopes at the
         // main pass's best
-        cur[k] = a.feas && q >= 2 ? (S.ph[q - 2][k - q * NH] != 0 ? 0.5f : 0.f) : par[k];
+        float c0 = a.feas && q >= 2 ? (S.ph[q - 2][k - q * NH] != 0 ? 0.5f : 0.f) : par[k];
+        // (untrusted: a slope is clamped to [0, 1] here -- NaN gives 0 --; bwd zeroes an unfixed neuron's
+        // multiplier and sends a negative one to the interval side; a NaN multiplier gives a NaN value,
+        // which closes nothing)
+        if (fpr) c0 = q < 2 ? fminf(fmaxf(fpr[k], 0.f), 1.f) : fpr[k];
+        cur[k] = c0;
         if (a.feas) cur[12 * NH + k] = cur[k];          // best iterate of the pass
         mom[k] = 0.f;
         vel[k] = 0.f;
@@ -543,6 +552,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FA_BETA_WPE
   if (lane < n0) {
     S.gt[0][lane] = my_ra && !a.feas ? gio[lane] : 0.f;
     S.gt[1][lane] = my_ra && !a.feas ? gio[n0 + lane] : 0.f;
+    if (fpr && a.fgt && my_ra) {       // the proposed tie multipliers, clamped to >= 0 (NaN gives 0)
+      S.gt[0][lane] = fmaxf(a.fgt[(size_t)r * 2 * n0 + lane], 0.f);
+      S.gt[1][lane] = fmaxf(a.fgt[(size_t)r * 2 * n0 + n0 + lane], 0.f);
+    }
     gbp = S.gt[0][lane];
     gbm = S.gt[1][lane];
   }
@@ -664,6 +677,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FA_BETA_WPE
                                                    nullptr);
     const double Bf = conc<double, true, false>(nd, S, N, S.cf[0], S.cf[1], kA, kB, eA + eB);
     if (lane == 0 && Bf > 0.0) a.bound[r] = __builtin_inf();
+    if (lane == 0 && a.fval) a.fval[r] = Bf;
     return;
   }
 

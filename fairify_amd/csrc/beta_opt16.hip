@@ -22,13 +22,22 @@
 // over the four lanes of the column in a fixed order, and nothing else crosses columns -- a node's
 // outputs are bitwise the same whatever shares its wave and whatever R is.
 //
+// Feas mode (template parameter FEAS; opt-in, BetaConfig.batched_feas): the proposal phase of the
+// infeasibility pass -- the `a.feas` branches of fa_beta_kernel, ops/beta.py:feasibility_ref.  Rows
+// that run: bound < 0, some phase fixed in either copy, not skipped, bounds not crossed.  Objective
+// weight 0 (the backward pass starts from a zero multiplier at the logit); a fixed neuron's multiplier
+// starts at 0.5, a free neuron's slope at par, the tie multipliers at 0, all projected to [0, 1]; t is
+// read, never updated (so the forward chain stops at the last hidden layer); no primal sums.  The best
+// iterate goes to BetaArgs::fpar / fgt -- par, t and gtie are only read: the children inherit the
+// main pass's best.  fa_beta_kernel at feas = 1, iters = 0 then decides on its rigorous fp64 value.
+//
 // Freeze rule: a column whose best value exceeds 0 stops updating (state, sums and parameters keep
 // their values; its lanes still run the wave's MFMAs).  The wave ends when every column is frozen or
 // after a.iters steps.  Skipped nodes, empty regions and crossed bounds are frozen from the start
 // and get no output (the second phase treats them as before).
 //
 // Registers (hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage), no scratch in
-// any instance: 1 tile 155 VGPRs, 2 tiles 219 (amdgpu_waves_per_eu 2: two waves per SIMD), 4 tiles
+// any instance (main mode; the feas instances: profiles/r8/feas16/README.md): 1 tile 155 VGPRs, 2 tiles 219 (amdgpu_waves_per_eu 2: two waves per SIMD), 4 tiles
 // 255 + 38 AGPRs, 7 tiles 256 + 74 AGPRs (hint 1: one wave per SIMD; at two waves per SIMD they
 // spill some 200 / 480 B per lane).  Four waves per workgroup (__launch_bounds__(256): the 4- and 7-tile
 // instances need more than 256 registers per lane); the staged weights allow 4 workgroups per CU
@@ -85,7 +94,8 @@ __device__ __forceinline__ float adam_dir(float m, float v, float ic1, float ic2
 #define FA_B16_WPE(TM) ((TM) <= 2 ? 2 : 1)
 #endif
 
-template <int TM>
+// FEAS: the proposal phase of the infeasibility pass (see the head of this file)
+template <int TM, bool FEAS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FA_B16_WPE(TM)))) void fa_beta_opt16_kernel(
     NetDesc nd, BetaArgs a, Opt16Cfg cfg) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -126,7 +136,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FA_B16_WPE(
   float* gio = tie ? a.gtie + (size_t)r * 2 * n0 : nullptr;
 
   // ---- pack the node's phase-clamped bounds, phases and start parameters; clear moments and sums
-  int bad = 0;
+  int bad = 0, fixd = 0;
   {
     const size_t phs = a.ph_stride > 0 ? (size_t)a.ph_stride : (size_t)NH;
     const float4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -151,7 +161,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FA_B16_WPE(
               f4(lb4, i) = lb;
               f4(ub4, i) = ub;
               f4(ph4, i) = (float)p;
-              f4(x4, i) = par[(p != 0 ? 2 + c : c) * NH + k];
+              if (p != 0) fixd = 1;
+              // (feas: a phase multiplier starts at 0.5, a slope at the main pass's best)
+              f4(x4, i) = FEAS && p != 0 ? 0.5f : par[(p != 0 ? 2 + c : c) * NH + k];
             }
           }
           const int s = cfg.slot[l] + t;
@@ -173,7 +185,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FA_B16_WPE(
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int d = 16 * t + 4 * grp + i;
-          if (d < n0 && ((ramask >> d) & 1ull)) {
+          if (!FEAS && d < n0 && ((ramask >> d) & 1ull)) {      // (feas: the tie multipliers start at 0)
             f4(gp4, i) = gio[d];
             f4(gm4, i) = gio[n0 + d];
           }
@@ -190,13 +202,40 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FA_B16_WPE(
     }
   }
   if (a.skip && a.skip[r]) bad = 1;
+  if (FEAS) {     // only nodes the main pass left open and that fix some phase
+    fixd |= __shfl_xor(fixd, 16, 64);
+    fixd |= __shfl_xor(fixd, 32, 64);
+    if (!fixd || !(a.bound[r] < 0.0)) bad = 1;
+  }
   bad |= __shfl_xor(bad, 16, 64);
   bad |= __shfl_xor(bad, 32, 64);
   const bool live = valid && !bad;          // a column that is optimised and gets outputs
   bool frozen = !live;
+  // feas: the best iterate goes to fpar / fgt (par, t and gtie stay the main pass's); every entry of
+  // a live row is defined from the start (the pass's start values: iters = 0 proposes those)
+  float* bpar = FEAS ? a.fpar + (size_t)r * 4 * NH : par;
+  if (FEAS && live) {
+    for (int c = 0; c < 2; ++c)
+      for (int l = 0; l < L - 1; ++l) {
+        const int w = nd.dims[l + 1], off = nd.neuron_off[l], tout = (w + 15) >> 4;
+        for (int t = 0; t < tout; ++t) {
+          const float4 ph4 = SQ(c, Q_PH, cfg.slot[l] + t), x4 = SQ(c, Q_X, cfg.slot[l] + t);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int j = 16 * t + 4 * grp + i;
+            if (j < w) {
+              const bool fx = (&ph4.x)[i] != 0.f;
+              bpar[c * NH + off + j] = fx ? par[c * NH + off + j] : (&x4.x)[i];
+              bpar[(2 + c) * NH + off + j] = fx ? (&x4.x)[i] : 0.f;
+            }
+          }
+        }
+      }
+  }
 
   float tc = a.t[r], tbest = tc, mt = 0.f, vt = 0.f;
-  const float og = a.osg ? (float)a.osg[r] : 1.f;
+  // (feas: objective weight 0 -- the backward pass starts from a zero multiplier at the logit)
+  const float og = FEAS ? 0.f : (a.osg ? (float)a.osg[r] : 1.f);
   float best = -FLT_MAX, nacc = 0.f;
   const float b1c = 0.9f, b2c = 0.999f;
   float p1 = 1.f, p2 = 1.f, dk = 1.f;
@@ -355,7 +394,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FA_B16_WPE(
     const bool upd = !frozen;
     if (!__any(upd || imp)) break;
     const float wi = a.pgap == 2 ? (float)(it + 1) : (a.pgap == 3 ? (2 * it >= a.iters ? 1.f : 0.f) : 1.f);
-    const bool acc = a.pgap && wi > 0.f;
+    const bool acc = !FEAS && a.pgap && wi > 0.f;       // (feas: no primal sums)
     p1 *= b1c;
     p2 *= b2c;
     const float ic1 = 1.f / (1.f - p1), ic2 = 1.f / (1.f - p2);
@@ -430,7 +469,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FA_B16_WPE(
               else if (kind == 2) h = x0 * z;
               else if (kind == 3) h = fdiv(ubj, ubj - lbj) * (z - lbj);
               H2[c][jt][i] = jv ? h : 0.f;
-              if (imp && jv) par[(pf != 0.f ? 2 + c : c) * NH + off + j] = x0;   // the best iterate
+              if (imp && jv) bpar[(pf != 0.f ? 2 + c : c) * NH + off + j] = x0;   // the best iterate
               if (upd && jv) {
                 if (acc) {
                   f4(zs4, i) += wi * z;
@@ -447,8 +486,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FA_B16_WPE(
                 f4(m4, i) = mm;
                 f4(v4, i) = vv;
                 const float nx = x0 + (pf != 0.f ? a.lr_b : a.lr_a) * dk * adam_dir(mm, vv, ic1, ic2);
-                // alpha projected to [0, 1]; beta >= 0 when beta_pos
-                f4(x4, i) = pf != 0.f ? (a.beta_pos ? fmaxf(nx, 0.f) : nx) : fminf(fmaxf(nx, 0.f), 1.f);
+                // alpha projected to [0, 1]; beta >= 0 when beta_pos (feas: to [0, 1] -- the value is
+                // homogeneous in the multipliers, a box keeps the scale fixed)
+                f4(x4, i) = (pf != 0.f && !FEAS) ? (a.beta_pos ? fmaxf(nx, 0.f) : nx) : fminf(fmaxf(nx, 0.f), 1.f);
               }
             }
             SQ(c, Q_X, s) = x4;
@@ -472,8 +512,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FA_B16_WPE(
           H[1][t][i] = H2[1][t][i];
         }
     }
-    float oA, oB;
-    {
+    float oA = 0.f, oB = 0.f;
+    if (!FEAS) {      // (feas: t is read, never updated -- no logit needed)
       const int tin = (nd.dims[L - 1] + 15) >> 4;
       const float4* wf4 = reinterpret_cast<const float4*>(smem + cfg.wf[L - 1]);
       f32x4 ZA = {0.f, 0.f, 0.f, 0.f}, ZB = ZA;
@@ -494,7 +534,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FA_B16_WPE(
       oA = __shfl(ZA[0] + bL, col, 64);
       oB = __shfl(ZB[0] + bL, col, 64);
     }
-    if (upd) {
+    if (!FEAS && upd) {
       if (acc) nacc += wi;
       const float gr = og * (oA + oB);
       mt = b1c * mt + (1.f - b1c) * gr;
@@ -520,8 +560,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FA_B16_WPE(
             f4(vp4, i) = vgp;
             f4(mm4, i) = mgm;
             f4(vm4, i) = vgm;
-            f4(gp4, i) = fminf(fmaxf((&gp4.x)[i] + a.lr_t * dk * adam_dir(mgp, vgp, ic1, ic2), 0.f), FLT_MAX);
-            f4(gm4, i) = fminf(fmaxf((&gm4.x)[i] + a.lr_t * dk * adam_dir(mgm, vgm, ic1, ic2), 0.f), FLT_MAX);
+            const float gmax = FEAS ? 1.f : FLT_MAX;
+            f4(gp4, i) = fminf(fmaxf((&gp4.x)[i] + a.lr_t * dk * adam_dir(mgp, vgp, ic1, ic2), 0.f), gmax);
+            f4(gm4, i) = fminf(fmaxf((&gm4.x)[i] + a.lr_t * dk * adam_dir(mgm, vgm, ic1, ic2), 0.f), gmax);
           }
         }
         SG(G_P, t) = gp4;
@@ -538,8 +579,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FA_B16_WPE(
   // ---- outputs: t and the tie multipliers of the best iterate (par was written when it improved),
   // the primal sums of every node (zero for the nodes left to the second phase)
   if (!valid) return;
-  if (live && a.iters > 0) {
-    if (grp == 0) a.t[r] = tbest;
+  if (live && (FEAS || a.iters > 0)) {
+    if (!FEAS && grp == 0) a.t[r] = tbest;
+    if (FEAS && tie) gio = a.fgt + (size_t)r * 2 * n0;
     if (tie) {
 #pragma unroll
       for (int t = 0; t < T0; ++t) {
@@ -555,6 +597,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FA_B16_WPE(
       }
     }
   }
+  if (FEAS) return;
   if (grp == 0) cfg.pgn[r] = nacc;
   float* pg = cfg.pgsum + (size_t)r * 4 * NH;
   for (int c = 0; c < 2; ++c)
@@ -576,8 +619,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FA_B16_WPE(
 #undef SG
 }
 
-FA_LDS_REGISTER(FA_LDS_K(fa_beta_opt16_kernel<1>), FA_LDS_K(fa_beta_opt16_kernel<2>),
-                FA_LDS_K(fa_beta_opt16_kernel<4>), FA_LDS_K(fa_beta_opt16_kernel<7>));
+FA_LDS_REGISTER(FA_LDS_K((fa_beta_opt16_kernel<1, false>)), FA_LDS_K((fa_beta_opt16_kernel<2, false>)),
+                FA_LDS_K((fa_beta_opt16_kernel<4, false>)), FA_LDS_K((fa_beta_opt16_kernel<7, false>)),
+                FA_LDS_K((fa_beta_opt16_kernel<1, true>)), FA_LDS_K((fa_beta_opt16_kernel<2, true>)),
+                FA_LDS_K((fa_beta_opt16_kernel<4, true>)), FA_LDS_K((fa_beta_opt16_kernel<7, true>)));
 
 // Tile depth, LDS offsets and scratch layout; false when the network is outside the kernel's limits.
 bool opt16_cfg(const NetDesc& nd, Opt16Cfg& cfg, int* tm, size_t* bytes) {
@@ -611,6 +656,22 @@ bool opt16_cfg(const NetDesc& nd, Opt16Cfg& cfg, int* tm, size_t* bytes) {
   return true;
 }
 
+// launches the instance of tile depth tm in the main (FEAS = false) or the feas mode
+template <bool FEAS>
+int opt16_run(const NetDesc& nd, const BetaArgs& a, const Opt16Cfg& cfg, int tm, size_t bytes, hipStream_t stream) {
+  const int ng = (a.R + 15) / 16;
+  const dim3 grid((ng + cfg.wpb - 1) / cfg.wpb), block(64 * cfg.wpb);
+  if (tm == 1)
+    hipLaunchKernelGGL((fa_beta_opt16_kernel<1, FEAS>), grid, block, bytes, stream, nd, a, cfg);
+  else if (tm == 2)
+    hipLaunchKernelGGL((fa_beta_opt16_kernel<2, FEAS>), grid, block, bytes, stream, nd, a, cfg);
+  else if (tm == 4)
+    hipLaunchKernelGGL((fa_beta_opt16_kernel<4, FEAS>), grid, block, bytes, stream, nd, a, cfg);
+  else
+    hipLaunchKernelGGL((fa_beta_opt16_kernel<7, FEAS>), grid, block, bytes, stream, nd, a, cfg);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
 }  // namespace
 
 extern "C" int fa_beta_opt16_fits(const NetDesc& nd) {
@@ -642,17 +703,38 @@ extern "C" int fa_beta_opt16_launch(const NetDesc& nd, BetaArgs a, float* pgsum,
   if (!fa_lds_ok(bytes)) return -2;
   cfg.pgsum = pgsum;
   cfg.pgn = pgn;
-  const int ng = (a.R + 15) / 16;
-  const dim3 grid((ng + cfg.wpb - 1) / cfg.wpb), block(64 * cfg.wpb);
-  if (tm == 1)
-    hipLaunchKernelGGL(fa_beta_opt16_kernel<1>, grid, block, bytes, stream, nd, a, cfg);
-  else if (tm == 2)
-    hipLaunchKernelGGL(fa_beta_opt16_kernel<2>, grid, block, bytes, stream, nd, a, cfg);
-  else if (tm == 4)
-    hipLaunchKernelGGL(fa_beta_opt16_kernel<4>, grid, block, bytes, stream, nd, a, cfg);
-  else
-    hipLaunchKernelGGL(fa_beta_opt16_kernel<7>, grid, block, bytes, stream, nd, a, cfg);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return opt16_run<false>(nd, a, cfg, tm, bytes, stream);
+}
+
+// The proposal phase of the infeasibility pass alone: a.iters steps on the phase constraints'
+// Lagrangian of the rows the main pass left open with a fixed phase (a.bound < 0), best iterate to
+// a.fpar [R, 4, NH] / a.fgt [R, 2, n0]; par / t / gtie / bound are only read.  Return codes as above.
+extern "C" int fa_beta_opt16_feas_launch(const NetDesc& nd, BetaArgs a, hipStream_t stream) {
+  Opt16Cfg cfg;
+  int tm = 0;
+  size_t bytes = 0;
+  if (!opt16_cfg(nd, cfg, &tm, &bytes) || a.npa > FA_MAX_PA) return -1;
+  const bool tie = a.plo && a.ramask && a.gtie;
+  if (!a.fpar || !a.bound || !a.scratch || (tie && !a.fgt)) return -4;
+  if (a.R <= 0) return 0;
+  if (!fa_lds_ok(bytes)) return -2;
+  cfg.pgsum = nullptr;
+  cfg.pgn = nullptr;
+  return opt16_run<true>(nd, a, cfg, tm, bytes, stream);
+}
+
+// The two-phase infeasibility pass: the proposal kernel, then fa_beta_kernel at feas = 1, iters = 0
+// on the same stream, which evaluates the rigorous fp64 value at the proposals and closes the row
+// (bound := +inf) when it is > 0.  a.scratch must hold max(R * 16 * NH, fa_beta_opt16_scratch_floats).
+extern "C" int fa_beta_feas16_launch(const NetDesc& nd, BetaArgs a, hipStream_t stream) {
+  a.feas = 1;
+  a.pgsum = nullptr;
+  a.pgn = nullptr;
+  const int rc = fa_beta_opt16_feas_launch(nd, a, stream);
+  if (rc != 0) return rc;
+  a.iters = 0;
+  const int r2 = fa_beta_launch(nd, a, stream);
+  return r2 == 0 ? 0 : r2 - 10;
 }
 
 // The two-phase level: the batched optimiser, then fa_beta_kernel at iters = 0 on the same stream

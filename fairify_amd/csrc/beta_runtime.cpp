@@ -32,6 +32,7 @@ extern "C" int fa_beta_launch(const NetDesc& nd, BetaArgs a, hipStream_t stream)
 extern "C" int fa_beta_opt16_fits(const NetDesc& nd);
 extern "C" size_t fa_beta_opt16_scratch_floats(const NetDesc& nd, int R);
 extern "C" int fa_beta_level16_launch(const NetDesc& nd, BetaArgs a, hipStream_t stream);
+extern "C" int fa_beta_feas16_launch(const NetDesc& nd, BetaArgs a, hipStream_t stream);
 extern "C" int fa_bb_count_launch(BetaPoolArgs a, hipStream_t s);
 extern "C" int fa_bb_rows_launch(BetaPoolArgs a, hipStream_t s);
 extern "C" int fa_bb_intersect_launch(BetaPoolArgs a, hipStream_t s);
@@ -132,6 +133,13 @@ class BetaRuntime {
       scratch_.ensure(std::max(B * 16 * nh_, fa_beta_opt16_scratch_floats(net_, batch_)));
       pgsum_.ensure(B * 4 * nh_);
       pgn_.ensure(B);
+    }
+    // batched_feas: the infeasibility pass in two phases too (proposals on MFMA, then the per-node kernel
+    // at iters = 0 decides on its rigorous value); static like `batched`, and only with it
+    batched_feas_ = batched_ && cfg.contains("batched_feas") && cfg["batched_feas"].cast<int>() != 0;
+    if (batched_feas_) {
+      fpar_.ensure((size_t)batch_ * 4 * nh_);
+      fgt_.ensure((size_t)batch_ * 2 * n0_);
     }
     status_.ensure(P); nodes_.ensure(P); probed_.ensure(P); part_closed_.ensure(P);
     tree_cnt_.ensure(std::max(R0, 1)); tree_done_.ensure(std::max(R0, 1)); tree_part_.ensure(std::max(R0, 1));
@@ -389,7 +397,7 @@ class BetaRuntime {
       a.pgsum = pgsum_.p;
       a.pgn = pgn_.p;
       rc = fa_beta_level16_launch(net_, a, st);
-      a.pgsum = nullptr;          // the infeasibility pass stays on the per-node kernel, unseeded
+      a.pgsum = nullptr;          // the infeasibility pass is unseeded
       a.pgn = nullptr;
     } else {
       rc = fa_beta_launch(net_, a, st);
@@ -401,7 +409,14 @@ class BetaRuntime {
       a.feas = 1;
       a.iters = feas_iters;
       a.lr_a = flr_a; a.lr_b = flr_b; a.lr_t = flr_t;     // a fresh optimisation: the roots' step sizes
-      const int rf = fa_beta_launch(net_, a, st);
+      int rf;
+      if (batched_feas_) {        // proposals 16 nodes per wave, then the rigorous decision per node
+        a.fpar = fpar_.p;
+        a.fgt = fgt_.p;
+        rf = fa_beta_feas16_launch(net_, a, st);
+      } else {
+        rf = fa_beta_launch(net_, a, st);
+      }
       if (rf != 0) throw std::runtime_error("fa_beta_kernel (feas) launch failed, code " + std::to_string(rf));
     }
   }
@@ -464,8 +479,8 @@ class BetaRuntime {
   Pool pool_[2];
   fa_exact::ExactChecker exact_;
   BBuf<uint8_t> skip_, infeas_, probed_, tree_done_;
-  bool batched_ = false;
-  BBuf<float> pgsum_, pgn_;
+  bool batched_ = false, batched_feas_ = false;
+  BBuf<float> pgsum_, pgn_, fpar_, fgt_;
   BBuf<float> scratch_, xstar_, xpstar_, binit_, rlo_, rhi_, cpts_, pe_lb_, pe_ub_;
   fa_rt::FormBufs form_;
   BBuf<double> bound_;

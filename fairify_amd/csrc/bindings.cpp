@@ -44,6 +44,8 @@ extern "C" int fa_beta_opt16_fits(const NetDesc& nd);
 extern "C" size_t fa_beta_opt16_scratch_floats(const NetDesc& nd, int R);
 extern "C" int fa_beta_opt16_launch(const NetDesc& nd, BetaArgs a, float* pgsum, float* pgn, hipStream_t stream);
 extern "C" int fa_beta_level16_launch(const NetDesc& nd, BetaArgs a, hipStream_t stream);
+extern "C" int fa_beta_opt16_feas_launch(const NetDesc& nd, BetaArgs a, hipStream_t stream);
+extern "C" int fa_beta_feas16_launch(const NetDesc& nd, BetaArgs a, hipStream_t stream);
 extern "C" int fa_knn_launch(const float* X, int n, int d, int k, int* idx, float* dist, hipStream_t stream);
 extern "C" int fa_actdiff_launch(const NetDesc& net, const float* flat, const float* x, const float* xp, int npairs,
                                  float* sum_out, hipStream_t stream);
@@ -608,6 +610,33 @@ PYBIND11_MODULE(_C, m) {
                                  iters, lr_a, lr_b, lr_t, decay, 0, beta_pos, (pgap & 3) << 1, 0, 0, 0, 0, ramask,
                                  plo, phi, 0, gtie, tau, osg);
     return fa_beta_opt16_launch(net.d, a, P<float>(pgsum), P<float>(pgn), reinterpret_cast<hipStream_t>(stream));
+  });
+  // the infeasibility pass alone on rows whose main-pass outputs (par, t, gtie, bound) are given.  mode 0:
+  // the per-node pass (fa_beta_kernel, feas = 1, `iters` steps; scratch [R, 16, NH]); 1: the two-phase
+  // pass (proposals to fpar [R, 4, NH] / fgt [R, 2, n0] by the batched optimiser's feas mode, then the
+  // per-node kernel at iters = 0 on them; scratch max(R * 16 * NH, beta_opt16_scratch(R))); 2: the
+  // proposal phase alone; 3: the rigorous phase alone on the fpar / fgt given.  fval [R] (optional):
+  // the rigorous value of the rows that ran.  bound: +inf written on the rows the pass closes
+  m.def("beta_feas", [beta_args](const Net& net, uintptr_t flat, uintptr_t wt, int R, std::vector<int> pa, uintptr_t lo,
+                                 uintptr_t hi, uintptr_t va, uintptr_t vb, uintptr_t LBA, uintptr_t UBA, uintptr_t LBB,
+                                 uintptr_t UBB, uintptr_t phA, uintptr_t phB, uintptr_t par, uintptr_t t,
+                                 uintptr_t scratch, int iters, float lr_a, float lr_b, float lr_t, float decay,
+                                 uintptr_t bound, unsigned long long ramask, uintptr_t plo, uintptr_t phi,
+                                 uintptr_t gtie, float tau, uintptr_t osg, uintptr_t fpar, uintptr_t fgt,
+                                 uintptr_t fval, int mode, uintptr_t stream) {
+    BetaArgs a = beta_args(net, flat, wt, R, pa, lo, hi, va, vb, LBA, UBA, LBB, UBB, phA, phB, par, t, scratch, iters,
+                           lr_a, lr_b, lr_t, decay, 0, 1, 8, bound, 0, 0, 0, ramask, plo, phi, 0, gtie, tau, osg);
+    if (mode < 0 || mode > 3) throw std::invalid_argument("beta_feas: mode must be 0..3");
+    if (mode != 0 && !fpar) throw std::invalid_argument("beta_feas: fpar required");
+    a.fval = P<double>(fval);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (mode == 0) return fa_beta_launch(net.d, a, st);
+    a.fpar = P<float>(fpar);
+    a.fgt = P<float>(fgt);
+    if (mode == 1) return fa_beta_feas16_launch(net.d, a, st);
+    if (mode == 2) return fa_beta_opt16_feas_launch(net.d, a, st);
+    a.iters = 0;
+    return fa_beta_launch(net.d, a, st);
   });
   m.def("beta_batched_fits", [](const Net& net) { return fa_beta_opt16_fits(net.d) != 0; });
   m.def("beta_opt16_scratch", [](const Net& net, int R) { return fa_beta_opt16_scratch_floats(net.d, R); });

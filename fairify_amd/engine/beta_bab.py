@@ -91,7 +91,14 @@ class BetaConfig:
     #                                  iters = 0 (rigorous bound, branching).  Used when the network fits
     #                                  the batched kernel (a static choice per network and config, never per
     #                                  level: verdicts do not depend on grouping); the infeasibility pass
-    #                                  stays per node; the CPU backend runs the torch reference unchanged
+    #                                  stays per node (unless batched_feas); the CPU backend runs the torch
+    #                                  reference unchanged
+    batched_feas: bool = os.environ.get("FAIRIFY_BETA_BATCHED_FEAS", "0") == "1"
+    #                                  with ``batched`` in effect: the infeasibility pass in two phases too --
+    #                                  the feas mode of the batched optimiser proposes the phase multipliers,
+    #                                  16 nodes per wave, and the per-node kernel at iters = 0 closes a node
+    #                                  when the rigorous fp64 value at them is > 0 (sound whatever is
+    #                                  proposed).  Static per (network, config) like ``batched``
     trees: tuple = ()                # experiment: only the trees (ordered-pair row, orientation) listed
     sign_prune: bool = True          # close the (pair, orientation) trees a per-value logit sign test settles
     #                                  before their roots are bounded
@@ -120,6 +127,10 @@ class BetaBaBSolver:
         self.be = backend
         self.q = query
         self.cfg = cfg
+        # the kernels' flags word holds the weights in two bits (ops/hip.py:beta_flags): a larger value
+        # would read as the infeasibility pass's bit
+        if not 0 <= int(cfg.pgap_weights) <= 3:
+            raise ValueError(f"BetaConfig.pgap_weights must be 0, 1, 2 or 3, got {cfg.pgap_weights!r}")
         self.tm = timer
         self.dev = backend.device
         self.stats = {}
@@ -243,6 +254,7 @@ class BetaBaBSolver:
         ia, ib = k * V + pr[:, 0], k * V + pr[:, 1]
         self.stats["native"] = self._use_native(O)       # the loop this group runs on (tests / logs)
         self.stats["batched"] = self._batched()
+        self.stats["batched_feas"] = self._batched_feas()
         if cfg.trees:        # experiment: one tree at a time (tools/exp/beta_vs_lp.py)
             jj = torch.arange(Pp, device=dev).repeat_interleave(O).repeat(run.size)
             sel = torch.zeros_like(k, dtype=torch.bool)
@@ -341,7 +353,8 @@ class BetaBaBSolver:
                                     cfg.beta_pos, rx, pgap=cfg.pgap_weights if cfg.branch == "pgap" else 0,
                                     osg=cur["osg"] if O > 1 else None,
                                     feas_iters=0 if is_root else cfg.feas_iters,
-                                    feas_lr=(cfg.lr_a, cfg.lr_b, cfg.lr_t), batched=self._batched())
+                                    feas_lr=(cfg.lr_a, cfg.lr_b, cfg.lr_t), batched=self._batched(),
+                                    batched_feas=self._batched_feas())
             if empty is not None:
                 lev.bound = torch.where(empty, torch.full_like(lev.bound, float("inf")), lev.bound)
             closed = lev.bound >= 0
@@ -417,6 +430,11 @@ class BetaBaBSolver:
 
         return hip.beta_batched_fits(self.be)
 
+    def _batched_feas(self) -> bool:
+        """The two-phase infeasibility pass (BetaConfig.batched_feas): on, the two-phase level in effect
+        and an infeasibility pass to run."""
+        return bool(self.cfg.batched_feas and self.cfg.feas_iters > 0 and self._batched())
+
     def _use_native(self, O: int) -> bool:
 
         cfg = self.cfg
@@ -455,7 +473,7 @@ class BetaBaBSolver:
                 "decay": float(cfg.decay), "lookahead": int(cfg.lookahead), "beta_pos": int(bool(cfg.beta_pos)),
                 "stall": 1, "pgap": int(cfg.pgap_weights) if cfg.branch == "pgap" else 0, "warm_beta": int(bool(cfg.warm_beta)),
                 "tighten": int(bool(cfg.tighten)), "feas_iters": int(cfg.feas_iters),
-                "batched": int(self._batched())}
+                "batched": int(self._batched()), "batched_feas": int(self._batched_feas())}
 
         confirm = exact.make_confirm(mlp_exact, lo_np, hi_np, q)
         cap = int(max(cfg.max_pool, 2 * R0))

@@ -320,8 +320,9 @@ def primal_gap_scores(zsum, hsum, n, lb, ub, ph):
 
 
 def feasibility_ref(ws32, bs32, widths, lo, hi, pa, va, vb, lbA, ubA, lbB, ubB, phA, phB, alA, alB, t, iters: int,
-                    lr_a: float, lr_b: float, lr_t: float, decay: float, rx, osg, run) -> torch.Tensor:
-    """[R] bool: rows whose phase region is proven EMPTY (the kernel's ``feas`` pass).
+                    lr_a: float, lr_b: float, lr_t: float, decay: float, rx, osg, run, value: bool = False):
+    """[R] bool: rows whose phase region is proven EMPTY (the kernel's ``feas`` pass); with ``value``
+    also the pass's rigorous fp64 value [R] (the mask is ``run & (value > 0)``).
 
     The Lagrangian of the fixed phases alone, ``min over the relaxed region of -sum_j beta_j s_j z_j``
     (plus the tau tie's multipliers on relaxed rows), is <= 0 whenever some point satisfies every
@@ -379,7 +380,8 @@ def feasibility_ref(ws32, bs32, widths, lo, hi, pa, va, vb, lbA, ubA, lbB, ubB, 
     ev = evaluate(ws64, bs64, lo.to(d), hi.to(d), pa, va.to(d), vb.to(d), (L64(lbA), L64(ubA)), (L64(lbB), L64(ubB)),
                   pA, pB, L64(fp["alA"]), L64(fp["alB"]), L64(fp["beA"]), L64(fp["beB"]), t.to(d), rig=True,
                   need_lin=False, rx=rxc(fp), osg=osg, obj=0.0)
-    return run & (ev["B"] > 0)
+    emp = run & (ev["B"] > 0)
+    return (emp, ev["B"]) if value else emp
 
 
 def clamp_bounds(LB: torch.Tensor, UB: torch.Tensor, ph: torch.Tensor):

@@ -702,16 +702,102 @@ def beta_opt16(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, b
     return par, t_o, (None if gt is None else gt[:, 0]), (None if gt is None else gt[:, 1]), pgsum, pgn
 
 
+def beta_flags(stall, pgap, feas: bool = False) -> int:
+    """The flags word of the ``beta_level`` bindings: bit 0 stall, bits 1-2 the primal-gap weights
+    (0 .. 3), bit 3 the infeasibility pass.  A ``pgap`` outside 0 .. 3 would spill into the pass's bit
+    (and the launch would then leave the main pass's outputs unwritten): it raises."""
+    pg = int(pgap)
+    if not 0 <= pg <= 3:
+        raise ValueError(f"beta: pgap (BetaConfig.pgap_weights) must be 0, 1, 2 or 3, got {pgap!r}")
+    return int(bool(stall)) | ((pg & 3) << 1) | (8 if feas else 0)
+
+
+def _feas_buffers(be, R, n0, NH, tie, batched, dev):
+    """(scratch, fpar, fgt) of an infeasibility pass on R rows (fpar / fgt: the two-phase pass only)."""
+    f32 = dict(dtype=torch.float32, device=dev)
+    nscr = R * 16 * NH
+    fpar = fgt = None
+    if batched:
+        nscr = max(nscr, int(ext().beta_opt16_scratch(_net(be), R)))
+        fpar = torch.zeros(R, 4, NH, **f32)
+        fgt = torch.zeros(R, 2, n0, **f32) if tie else None
+    return torch.empty(max(nscr, 1), **f32), fpar, fgt
+
+
+def beta_feas(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, t, bound, iters, lr, batched: bool,
+              decay=1.0, rx=None, osg=None, proposal=None, return_proposal=False):
+    """The infeasibility pass alone (ops/beta.py:feasibility_ref) on rows whose main pass is done:
+    ``alA / alB / t`` (and ``rx``'s tie multipliers, which the pass only needs to exist) are the main
+    pass's best, ``bound`` [R] float64 its bounds -- rows with ``bound < 0`` and a fixed phase run.
+    ``lr`` = (lr_a, lr_b, lr_t).  ``batched`` False: the per-node pass (``fa_beta_kernel``, feas = 1);
+    True: the two-phase pass -- proposals by the feas mode of ``fa_beta_opt16_kernel``, 16 nodes per
+    wave, then ``fa_beta_kernel`` at iters = 0 decides on its rigorous fp64 value at them.
+    ``proposal`` = (fpar [R, 4, NH], fgt [R, 2, n0] or None): the rigorous phase alone on these
+    (untrusted) parameters.  Nothing is modified in place.  Returns ``(closed [R] bool, value [R]
+    float64)`` -- value NaN on the rows that did not run --, with ``return_proposal`` also
+    ``(fpar, fgt)`` as the proposal phase wrote them (zero where it wrote nothing)."""
+    R, n0 = lo.shape
+    NH = be.n_hidden
+    dev = lo.device
+    npa = len(pa)
+    if list(pa) != sorted(pa):
+        raise ValueError("beta_feas: PA dims must be increasing")
+    two_phase = bool(batched) or proposal is not None
+    if two_phase and not beta_batched_fits(be):
+        raise RuntimeError("fa_beta_opt16_kernel: network not supported by the batched beta optimiser")
+    lo_c = _c(lo, torch.float32, (R, n0), "lo")
+    hi_c = _c(hi, torch.float32, (R, n0), "hi")
+    va_c = _c(va, torch.float32, (R, npa), "va")
+    vb_c = _c(vb, torch.float32, (R, npa), "vb")
+    bnd = [_c(x, torch.float32, (R, NH), nm) for x, nm in ((LBA, "LBA"), (UBA, "UBA"), (LBB, "LBB"), (UBB, "UBB"))]
+    pA = _c(phA, torch.int8, (R, NH), "phA")
+    pB = _c(phB, torch.int8, (R, NH), "phB")
+    for x, nm in ((alA, "alA"), (alB, "alB")):
+        if tuple(x.shape) != (R, NH) or x.dtype != torch.float32:
+            raise ValueError(f"{nm}: expected float32 [{R}, {NH}]")
+    z = torch.zeros_like(alA)
+    par = torch.stack([alA, alB, z, z], 1).contiguous()
+    t_c = _c(t, torch.float32, (R,), "t").clone()
+    bnd_o = _c(bound, torch.float64, (R,), "bound").clone()
+    ramask, plo_c, phi_c, gt, tau = _rx_args(rx, R, n0)
+    osg_c = None if osg is None else _c(osg, torch.int8, (R,), "osg")
+    fval = torch.full((R,), float("nan"), dtype=torch.float64, device=dev)
+    scratch, fpar, fgt = _feas_buffers(be, R, n0, NH, gt is not None, two_phase, dev)
+    mode = 1 if batched else 0
+    if proposal is not None:
+        mode = 3
+        fpar = _c(proposal[0], torch.float32, (R, 4, NH), "fpar").clone()
+        if gt is not None:
+            fgt = _c(proposal[1], torch.float32, (R, 2, n0), "fgt").clone()
+    if R:
+        rc = ext().beta_feas(_net(be), be.flat.data_ptr(), _beta_wt(be).data_ptr(), R, [int(d) for d in pa],
+                             lo_c.data_ptr(), hi_c.data_ptr(), va_c.data_ptr(), vb_c.data_ptr(),
+                             *[x.data_ptr() for x in bnd], pA.data_ptr(), pB.data_ptr(), par.data_ptr(),
+                             t_c.data_ptr(), scratch.data_ptr(), int(iters), float(lr[0]), float(lr[1]), float(lr[2]),
+                             float(decay), bnd_o.data_ptr(), int(ramask), _ptr(plo_c), _ptr(phi_c), _ptr(gt),
+                             float(tau), _ptr(osg_c), _ptr(fpar), _ptr(fgt), fval.data_ptr(), mode, _stream(dev))
+        if rc != 0:
+            raise RuntimeError(f"beta_feas launch failed ({rc})")
+    closed = torch.isinf(bnd_o) & (bnd_o > 0) & ~(torch.isinf(bound) & (bound > 0))
+    if return_proposal:
+        return closed, fval, (fpar, fgt)
+    return closed, fval
+
+
 def beta_level(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, beA, beB, t, iters, lr_a, lr_b, lr_t,
                decay=1.0, lookahead=0, beta_pos=True, rx=None, stall=True, pgap=False, osg=None, feas_iters=0,
-               feas_lr=None, batched=False):
+               feas_lr=None, batched=False, batched_feas=False):
     """One beta-CROWN BaB level on the device (``fa_beta_kernel``, csrc/beta.hip): the rows'
     (alpha, beta, t) are optimised IN PLACE (kept at the best iterate) and their rigorous fp64
     bounds, branching decisions, concretising vertices and child multipliers returned
     (:class:`ops.beta.BetaLevel`).  ``batched``: the two-phase level -- the optimisation on MFMA, 16
     nodes per wave (csrc/beta_opt16.hip), then this kernel at ``iters = 0`` for the rigorous bound and
-    the branching; a network the batched kernel cannot run raises."""
+    the branching; a network the batched kernel cannot run raises.  ``batched_feas`` (with ``batched``):
+    the infeasibility pass in two phases too (:func:`beta_feas`)."""
     from . import beta as B
+
+    flags = beta_flags(stall, pgap)
+    batched_feas = bool(batched and batched_feas and feas_iters > 0)
 
     R, n0 = lo.shape
     NH = be.n_hidden
@@ -742,6 +828,9 @@ def beta_level(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, b
         pgsum = torch.empty(R, 4, NH, **f32)
         pgn = torch.empty(R, **f32)
     scratch = torch.empty(max(nscr, 1), **f32)
+    fpar = fgt = None
+    if batched_feas:
+        fpar = torch.empty(R, 4, NH, **f32)
     bound = torch.empty(R, dtype=torch.float64, device=dev)
     split = torch.empty(R, dtype=torch.int32, device=dev)
     xstar = torch.empty(R, n0, **f32)
@@ -749,6 +838,8 @@ def beta_level(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, b
     xpstar = torch.empty(R, n0, **f32)
     ramask, plo_c, phi_c, gt, tau = _rx_args(rx, R, n0)
     osg_c = None if osg is None else _c(osg, torch.int8, (R,), "osg")
+    if batched_feas and gt is not None:
+        fgt = torch.empty(R, 2, n0, **f32)
     if R:
         def launch(n_it, flags, lra, lrb, lrt, two_phase=False):
             args = (_net(be), be.flat.data_ptr(), _beta_wt(be).data_ptr(), R, [int(d) for d in pa],
@@ -762,10 +853,19 @@ def beta_level(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, b
                 return ext().beta_level16(*args, pgsum.data_ptr(), pgn.data_ptr(), _stream(dev))
             return ext().beta_level(*args, _stream(dev))
 
-        rc = launch(iters, int(bool(stall)) | (int(pgap) << 1), lr_a, lr_b, lr_t, two_phase=bool(batched))
-        if rc == 0 and feas_iters > 0:
+        rc = launch(iters, flags, lr_a, lr_b, lr_t, two_phase=bool(batched))
+        if rc == 0 and batched_feas:
+            # the two-phase infeasibility pass: proposals on MFMA, the rigorous decision per node
+            fl = feas_lr or (lr_a, lr_b, lr_t)
+            rc = ext().beta_feas(_net(be), be.flat.data_ptr(), _beta_wt(be).data_ptr(), R, [int(d) for d in pa],
+                                 lo_c.data_ptr(), hi_c.data_ptr(), va_c.data_ptr(), vb_c.data_ptr(),
+                                 *[x.data_ptr() for x in bnd], pA.data_ptr(), pB.data_ptr(), par.data_ptr(),
+                                 t.data_ptr(), scratch.data_ptr(), int(feas_iters), float(fl[0]), float(fl[1]),
+                                 float(fl[2]), float(decay), bound.data_ptr(), int(ramask), _ptr(plo_c), _ptr(phi_c),
+                                 _ptr(gt), float(tau), _ptr(osg_c), fpar.data_ptr(), _ptr(fgt), 0, 1, _stream(dev))
+        elif rc == 0 and feas_iters > 0:
             # the infeasibility pass (bit 3) on the nodes left open: only their bounds can change
-            rc = launch(feas_iters, 8, *(feas_lr or (lr_a, lr_b, lr_t)))
+            rc = launch(feas_iters, beta_flags(False, 0, feas=True), *(feas_lr or (lr_a, lr_b, lr_t)))
         if rc != 0:
             raise RuntimeError(f"fa_beta_kernel launch failed ({rc}): network not supported by the beta kernel")
         if gt is not None:

@@ -8,8 +8,13 @@ point of the box (so the regions are non-empty and the optimiser runs its full c
 Arms alternate on one device; times are device times between events, parameters re-initialised
 outside the timed region.
 
+Infeasibility arm (--feas-iters, default 64; 0: off): the pass alone (hip.beta_feas) on the rows the
+per-node level leaves open with a fixed phase, at that level's best parameters and the roots' step
+sizes -- the per-node pass against the two-phase one (proposals by the feas mode of
+fa_beta_opt16_kernel, decision by fa_beta_kernel at iters = 0); closed counts of both reported.
+
     python tools/bench_beta_level.py [--nets AC-7,BM-8,AC-4] [--R 32768] [--iters 128] [--lookahead 8]
-                                     [--runs 3] [--json PATH]
+                                     [--runs 3] [--feas-iters 64] [--json PATH]
 """
 import argparse
 import json
@@ -89,6 +94,7 @@ def main():
     ap.add_argument("--iters", type=int, default=128)
     ap.add_argument("--lookahead", type=int, default=8)
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--feas-iters", type=int, default=64)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda")
@@ -124,6 +130,29 @@ def main():
                    batched_phase1_ms=t1, per_node_closed=ca, batched_closed=cb,
                    mean_bound_per_node=float(la.bound[torch.isfinite(la.bound)].mean()),
                    mean_bound_batched=float(lb.bound[torch.isfinite(lb.bound)].mean()))
+        if a.feas_iters > 0:
+            al, be_, t = fresh(ns, dev)
+            lev = hip.beta_level(be, *common, al[0], al[1], be_[0], be_[1], t, a.iters, decay=0.98,
+                                 lookahead=a.lookahead, pgap=1, osg=ns["osg"], **lr)
+            fixed = (ns["ph"][0] != 0).any(1) | (ns["ph"][1] != 0).any(1)
+            idx = torch.nonzero((lev.bound < 0) & fixed).flatten()
+            sub = [x[idx].contiguous() for x in common[:2] + common[3:]]
+            rest = (al[0][idx].contiguous(), al[1][idx].contiguous(), t[idx].contiguous(), lev.bound[idx].contiguous())
+
+            def feas(batched):
+                return timed(lambda: hip.beta_feas(be, sub[0], sub[1], ns["pa"], *sub[2:], *rest, a.feas_iters,
+                                                   (0.1, 0.5, 0.1), batched, decay=0.98, osg=ns["osg"][idx]), dev)
+
+            tFa, tFb, fa, fb = [], [], None, None
+            if idx.numel():
+                feas(False), feas(True)
+                for _ in range(a.runs):
+                    msA, fa = feas(False)
+                    msB, fb = feas(True)
+                    tFa.append(msA), tFb.append(msB)
+            row.update(feas_iters=a.feas_iters, feas_rows=int(idx.numel()), feas_per_node_ms=tFa, feas_batched_ms=tFb,
+                       feas_per_node_closed=int(fa[0].sum()) if fa else 0,
+                       feas_batched_closed=int(fb[0].sum()) if fb else 0)
         rows.append(row)
         print(json.dumps(row), flush=True)
     if a.json:
