@@ -159,6 +159,8 @@ struct SimArgs {
   int* keys;                // [P] first-flip key scratch (INT_MAX-initialised) when split > 1
   int split;                // workgroups per partition (sample tiles strided over them)
   int S;
+  int regcount;             // 1: networks with a compile-time-shape instance (forward.hip) count their
+                            // activations in registers; 0: the run-time-shape kernel for every network
 };
 
 struct CertArgs {

@@ -23,6 +23,7 @@ extern "C" size_t fa_crown_phase_bytes(const NetDesc& net);
 extern "C" int fa_point_try_launch(const NetDesc& net, BoundArgs a, hipStream_t stream);
 extern "C" int fa_forward_launch(const NetDesc& net, FwdArgs a, hipStream_t stream);
 extern "C" int fa_sim_launch(const NetDesc& net, SimArgs a, hipStream_t stream);
+extern "C" int fa_sim_shaped(const NetDesc& net);
 extern "C" int fa_ascent_launch(const NetDesc& net, AscentArgs a, hipStream_t stream);
 extern "C" int fa_certify_launch(CertArgs a, hipStream_t stream);
 extern "C" int fa_falsify_launch(const NetDesc& net, FalsifyArgs a, hipStream_t stream);
@@ -310,7 +311,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("sim", [](const Net& net, uintptr_t flat, uintptr_t lo, uintptr_t hi, uintptr_t pids, int Pn, int n_samples,
                   uint32_t seed, int V, const std::vector<int>& pa, uintptr_t values, int Pp, uintptr_t pairs,
                   const std::vector<int>& ra, int tau, uintptr_t counts, uintptr_t found, uintptr_t wit_x,
-                  uintptr_t wit_xp, uintptr_t z0, uintptr_t keys, int split, uintptr_t stream) {
+                  uintptr_t wit_xp, uintptr_t z0, uintptr_t keys, int split, int regcount, uintptr_t stream) {
     if (pa.size() > FA_MAX_PA || ra.size() > FA_MAX_RA) throw std::invalid_argument("too many PA/RA dims");
     if (split < 1 || (split > 1 && !keys)) throw std::invalid_argument("sim: split > 1 needs a keys buffer");
     SimArgs a{};
@@ -337,8 +338,10 @@ PYBIND11_MODULE(_C, m) {
     a.z0 = P<float>(z0);
     a.keys = P<int>(keys);
     a.split = split;
+    a.regcount = regcount;
     ckl(fa_sim_launch(net.d, a, (hipStream_t)stream), "sim");
   });
+  m.def("sim_shaped", [](const Net& net) { return fa_sim_shaped(net.d) != 0; });
 
   // returns false if the partition's candidate rows do not fit in LDS (caller keeps PyTorch)
   m.def("ascent", [](const Net& net, uintptr_t flat, uintptr_t lo, uintptr_t hi, uintptr_t x0, uintptr_t f0,

@@ -175,7 +175,7 @@ __global__ void __launch_bounds__(FA_THREADS) fa_falsify_kernel(NetDesc net, Fal
   const int V = a.V, Pp = a.Pp;
   const bool rx = fa_fals_relaxed(a);
   const int RV = rx ? 2 * V : V;
-  fa_stage_wperm(net, a.flat, smem, tid, FA_THREADS);
+  fa_stage_wperm(net, cfg, a.flat, smem, tid, FA_THREADS);
   for (int i = tid; i < n0; i += FA_THREADS) {
     s_lo[i] = a.lo[(size_t)p * n0 + i];
     s_hi[i] = a.hi[(size_t)p * n0 + i];

@@ -276,6 +276,8 @@ __global__ void __launch_bounds__(FA_THREADS) fa_sim_finalize_kernel(NetDesc net
 // flip differently (counts stay within the rounding margins of tests/test_kernels_gpu.py).
 // Relaxed queries add V passes of x' rows (fa_sim_kernel's offsets: x'_r = x_r + d, d uniform in
 // [-tau, tau] from the seed ^ 0x2545F491 stream, unclipped), which are not counted.
+// Networks with a compile-time-shape instance (select_sim_shaped) keep the counts in registers
+// instead and flush them once per workgroup: the same integers.
 
 // One layer with activation counting: H -> H2 (ReLU outputs); counts neuron j for the samples
 // whose lanes have `match` (the sampled PA tuple is this pass's values[v]); last layer: the logit
@@ -327,11 +329,146 @@ __device__ __forceinline__ float fa_reg_layer_count(const NetDesc& net, const Re
   return logit;
 }
 
-template <int TM>
+// Compile-time network shape (common.h FaShape): the staged block's offsets (fa_regnet_cfg's
+// formulas), the all-neuron numbering and the lane's activation counters as constants.  Counter
+// creg(l) + 4 jt + i belongs to neuron 16 jt + 4 (lane>>4) + i of hidden layer l; the last one to
+// the logit.
+template <class S>
+struct SimShape {
+  static constexpr int tiles(int l) { return (S::dim(l) + 15) / 16; }
+  static constexpr int tm() {
+    int m = 1;
+    for (int l = 0; l <= S::L; ++l) m = m > tiles(l) ? m : tiles(l);
+    return m;
+  }
+  static constexpr int w_lds(int l) {
+    int off = 0;
+    for (int k = 0; k < l; ++k) off += tiles(k) * tiles(k + 1) * 256;
+    return off;
+  }
+  static constexpr int b_lds(int l) {
+    int off = w_lds(S::L);
+    for (int k = 0; k < l; ++k) off += S::dim(k + 1);
+    return off;
+  }
+  static constexpr int bp_lds(int l) {
+    int off = (b_lds(S::L) + 3) & ~3;
+    for (int k = 0; k < l; ++k) off += 16 * tiles(k + 1);
+    return off;
+  }
+  static constexpr int neuron_off(int l) {
+    int off = 0;
+    for (int k = 0; k < l; ++k) off += S::dim(k + 1);
+    return off;
+  }
+  static constexpr int creg(int l) {
+    int off = 0;
+    for (int k = 0; k < l; ++k) off += 4 * tiles(k + 1);
+    return off;
+  }
+  static constexpr int n_creg() { return creg(S::L - 1) + 1; }
+};
+
+// Layers l .. L-1 of a compile-time shape, unrolled by recursion (H -> H2 -> H ...): the MFMA chains
+// and `Z[i] + b` of fa_reg_layer_count in the same order (bitwise the same activations and logit),
+// but the lane only adds `match && h != 0` to its own counter C[] -- no ballot, no LDS traffic; the
+// workgroup reduces the counters once after its sample loop (fa_sim_flush_counts).  The lane's four
+// biases of a tile are read ahead of the tile's chain with one unguarded 16-byte read of the
+// zero-padded copy (regfwd.h), so the chain covers the LDS wait; the bias stays a separate add after
+// the chain: starting the accumulator at the bias would round differently.
+template <class S, int l, int TM>
+__device__ __forceinline__ float fa_reg_layers_count_shaped(const float* sw_all, int lane, float (&H)[TM][4],
+                                                            float (&H2)[TM][4], bool match,
+                                                            int (&C)[SimShape<S>::n_creg()]) {
+  using SS = SimShape<S>;
+  constexpr int n_out = S::dim(l + 1), tin = SS::tiles(l), tout = SS::tiles(l + 1);
+  const int grp = lane >> 4;
+  const float4* sw = reinterpret_cast<const float4*>(sw_all + SS::w_lds(l)) + lane;
+  const float* sb = sw_all + SS::b_lds(l);
+  if constexpr (l == S::L - 1) {
+    static_assert(n_out == 1, "one logit");
+    const float b0 = sb[0];
+    f32x4 Z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < tin; ++t) {
+      const float4 w4 = sw[t * 64];
+      Z = fa_mfma4(w4.x, H[t][0], Z);
+      Z = fa_mfma4(w4.y, H[t][1], Z);
+      Z = fa_mfma4(w4.z, H[t][2], Z);
+      Z = fa_mfma4(w4.w, H[t][3], Z);
+    }
+    const float logit = Z[0] + b0;
+    C[SS::creg(l)] += (match && logit != 0.f) ? 1 : 0;   // lane group 0 holds the logit row
+    return logit;
+  } else {
+#pragma unroll
+    for (int jt = 0; jt < tout; ++jt) {
+      constexpr bool kFull = n_out % 16 == 0;
+      const bool full = kFull || jt < tout - 1;            // constant after unrolling
+      const float4 b4 = *reinterpret_cast<const float4*>(sw_all + SS::bp_lds(l) + 16 * jt + 4 * grp);
+      const float b[4] = {b4.x, b4.y, b4.z, b4.w};
+      f32x4 Z = {0.f, 0.f, 0.f, 0.f};
+      const float4* wq = sw + jt * tin * 64;
+#pragma unroll
+      for (int t = 0; t < tin; ++t) {
+        const float4 w4 = wq[t * 64];
+        Z = fa_mfma4(w4.x, H[t][0], Z);
+        Z = fa_mfma4(w4.y, H[t][1], Z);
+        Z = fa_mfma4(w4.z, H[t][2], Z);
+        Z = fa_mfma4(w4.w, H[t][3], Z);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int j = 16 * jt + 4 * grp + i;
+        float h = fmaxf(Z[i] + b[i], 0.f);
+        if (!full) h = j >= n_out ? 0.f : h;
+        H2[jt][i] = h;
+        C[SS::creg(l) + 4 * jt + i] += (match && h != 0.f) ? 1 : 0;
+      }
+    }
+    return fa_reg_layers_count_shaped<S, l + 1, TM>(sw_all, lane, H2, H, match, C);
+  }
+}
+
+// Once per workgroup: each counter summed over the 16 lanes of its lane group (the 16 samples of
+// the wave that share the neuron), one LDS add per neuron and wave.
+template <class S, int l>
+__device__ __forceinline__ void fa_sim_flush_counts(int lane, const int (&C)[SimShape<S>::n_creg()], int* cnt) {
+  using SS = SimShape<S>;
+  const int grp = lane >> 4, col = lane & 15;
+  if constexpr (l == S::L - 1) {
+    int c = grp == 0 ? C[SS::creg(l)] : 0;
+    c += __shfl_xor(c, 1);
+    c += __shfl_xor(c, 2);
+    c += __shfl_xor(c, 4);
+    c += __shfl_xor(c, 8);
+    if (lane == 0 && c) atomicAdd(&cnt[SS::neuron_off(l)], c);
+  } else {
+    constexpr int n_out = S::dim(l + 1);
+#pragma unroll
+    for (int jt = 0; jt < SS::tiles(l + 1); ++jt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int j = 16 * jt + 4 * grp + i;
+        int c = C[SS::creg(l) + 4 * jt + i];
+        c += __shfl_xor(c, 1);
+        c += __shfl_xor(c, 2);
+        c += __shfl_xor(c, 4);
+        c += __shfl_xor(c, 8);
+        if (col == 0 && j < n_out && c) atomicAdd(&cnt[SS::neuron_off(l) + j], c);
+      }
+    fa_sim_flush_counts<S, l + 1>(lane, C, cnt);
+  }
+}
+
+// S = FaShapeAny: widths from NetDesc, counts by ballot per site (fa_reg_layer_count).  S = FaShape<...>
+// (TM = its tile depth): layer loop unrolled with constant widths, counts in registers.
+template <int TM, class S = FaShapeAny>
 __global__ void __launch_bounds__(FA_THREADS) fa_sim_reg_kernel(NetDesc net, SimArgs a, RegNetCfg cfg) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, grp = lane >> 4;
-  const int n0 = net.dims[0];
+  constexpr bool kShaped = S::L > 0;
+  const int n0 = kShaped ? S::dim(0) : net.dims[0];
   const int G = a.split;
   const int p = blockIdx.x / G;
   const int g = blockIdx.x - p * G;
@@ -345,7 +482,7 @@ __global__ void __launch_bounds__(FA_THREADS) fa_sim_reg_kernel(NetDesc net, Sim
   float* s_hi = s_lo + n0;
   int* cnt = (int*)(s_hi + n0);               // [n_neurons]
   int* best = cnt + net.n_neurons;
-  fa_stage_wperm(net, a.flat, smem, tid, FA_THREADS);
+  fa_stage_wperm(net, cfg, a.flat, smem, tid, FA_THREADS);
   for (int i = tid; i < n0; i += FA_THREADS) {
     s_lo[i] = a.lo[(size_t)p * n0 + i];
     s_hi[i] = a.hi[(size_t)p * n0 + i];
@@ -367,6 +504,11 @@ __global__ void __launch_bounds__(FA_THREADS) fa_sim_reg_kernel(NetDesc net, Sim
         if (a.pa_idx[m] == k) q = m;
       pslot[t][i] = (int8_t)q;
     }
+  int C[SimShape<S>::n_creg()];
+  if constexpr (kShaped) {
+#pragma unroll
+    for (int c = 0; c < SimShape<S>::n_creg(); ++c) C[c] = 0;
+  }
   for (int s0 = g * FA_TR; s0 < a.n_samples; s0 += G * FA_TR) {
     const int s = s0 + wave * 16 + col;
     const bool sv = s < a.n_samples;
@@ -412,9 +554,13 @@ __global__ void __launch_bounds__(FA_THREADS) fa_sim_reg_kernel(NetDesc net, Sim
           HA[t][i] = x;
         }
       float z = 0.f;
-      for (int l = 0; l < net.n_layers; ++l) {
-        if (l & 1) z = fa_reg_layer_count<TM>(net, cfg, smem, l, lane, HB, HA, match, cnt);
-        else z = fa_reg_layer_count<TM>(net, cfg, smem, l, lane, HA, HB, match, cnt);
+      if constexpr (kShaped) {
+        z = fa_reg_layers_count_shaped<S, 0, TM>(smem, lane, HA, HB, match, C);
+      } else {
+        for (int l = 0; l < net.n_layers; ++l) {
+          if (l & 1) z = fa_reg_layer_count<TM>(net, cfg, smem, l, lane, HB, HA, match, cnt);
+          else z = fa_reg_layer_count<TM>(net, cfg, smem, l, lane, HA, HB, match, cnt);
+        }
       }
       if (grp == 0) zs[(wave * 16 + col) * RV + v2] = z;   // read back by this same lane only
     }
@@ -430,6 +576,7 @@ __global__ void __launch_bounds__(FA_THREADS) fa_sim_reg_kernel(NetDesc net, Sim
       }
     }
   }
+  if constexpr (kShaped) fa_sim_flush_counts<S, 0>(lane, C, cnt);
   __syncthreads();
   const int key = best[0];
   if (G > 1) {
@@ -453,6 +600,41 @@ SimRegKernel select_sim_reg(int TM) {
   if (TM <= 10) return fa_sim_reg_kernel<10>;   // BM-4 (150-wide); the 64-row tile kernel before
   return nullptr;
 }
+// Compile-time shapes (common.h FaShape): the chains of AC-1 .. AC-12.  Same LDS layout, samples,
+// passes and arithmetic as the run-time-shape kernel of the same tile depth; SimArgs.regcount = 0
+// (FAIRIFY_SIM_REGCOUNT=0, per call) keeps that kernel.
+struct ShapedSim {
+  std::vector<int> dims;
+  SimRegKernel k;
+};
+template <int... D>
+ShapedSim shaped_sim() {
+  using S = FaShape<D...>;
+  return {{D...}, fa_sim_reg_kernel<SimShape<S>::tm(), S>};
+}
+#define FA_SIM_SHAPES(X)                                                                        \
+  X(13, 100, 100, 1) X(13, 100, 1) X(13, 64, 32, 16, 8, 4, 1) X(13, 64, 64, 1) X(13, 50, 1)     \
+  X(13, 16, 8, 1) X(13, 12, 12, 1) X(13, 10, 10, 10, 10, 1) X(13, 5, 5, 1) X(13, 5, 5, 5, 5, 1)   \
+  X(13, 3, 3, 3, 3, 1) X(13, 5, 5, 5, 5, 5, 5, 5, 5, 5, 1)
+SimRegKernel select_sim_shaped(const NetDesc& net) {
+#define FA_SIM_ENTRY(...) shaped_sim<__VA_ARGS__>(),
+  static const std::vector<ShapedSim> v = {FA_SIM_SHAPES(FA_SIM_ENTRY)};
+#undef FA_SIM_ENTRY
+  for (const auto& s : v) {
+    if ((int)s.dims.size() != net.n_layers + 1) continue;
+    bool same = true;
+    int noff = 0;
+    for (int l = 0; l <= net.n_layers && same; ++l) {
+      same = s.dims[l] == net.dims[l];
+      if (l < net.n_layers) {
+        same = same && net.neuron_off[l] == noff;   // the constants assume the dense numbering
+        noff += s.dims[l + 1];
+      }
+    }
+    if (same) return s.k;
+  }
+  return nullptr;
+}
 // A/B switch (FAIRIFY_SIM_REG=0: the 64-row LDS tile kernel for every query)
 bool sim_reg_on() {
   static const bool v = [] {
@@ -463,6 +645,9 @@ bool sim_reg_on() {
 }
 }  // namespace
 
+// does a compile-time-shape instance of the simulation kernel exist for this network?
+extern "C" int fa_sim_shaped(const NetDesc& net) { return select_sim_shaped(net) != nullptr; }
+
 extern "C" int fa_sim_launch(const NetDesc& net, SimArgs a, hipStream_t stream) {
   if (a.P <= 0) return 0;
   if (a.npa > FA_MAX_PA || a.nra > FA_MAX_RA) return -3;
@@ -470,7 +655,8 @@ extern "C" int fa_sim_launch(const NetDesc& net, SimArgs a, hipStream_t stream) 
   a.S = net.max_width | 1;
   const int n0 = net.dims[0];
   if (sim_reg_on()) {
-    const SimRegKernel k = select_sim_reg(fa_regnet_tm(net));
+    SimRegKernel k = a.regcount ? select_sim_shaped(net) : nullptr;
+    if (!k) k = select_sim_reg(fa_regnet_tm(net));
     RegNetCfg cfg{};
     if (k && fa_regnet_cfg(net, cfg)) {
       const size_t RV = a.nra > 0 ? 2 * (size_t)a.V : (size_t)a.V;
@@ -636,3 +822,6 @@ extern "C" int fa_ascent_launch(const NetDesc& net, AscentArgs a, hipStream_t st
 FA_LDS_REGISTER(FA_LDS_K(fa_forward_kernel), FA_LDS_K(fa_sim_kernel), FA_LDS_K(fa_ascent_kernel),
                 FA_LDS_K(fa_sim_reg_kernel<1>), FA_LDS_K(fa_sim_reg_kernel<2>), FA_LDS_K(fa_sim_reg_kernel<4>),
                 FA_LDS_K(fa_sim_reg_kernel<7>), FA_LDS_K(fa_sim_reg_kernel<10>));
+#define FA_SIM_LDS(...) FA_LDS_K((fa_sim_reg_kernel<SimShape<FaShape<__VA_ARGS__>>::tm(), FaShape<__VA_ARGS__>>)),
+FA_LDS_REGISTER(FA_SIM_SHAPES(FA_SIM_LDS));
+#undef FA_SIM_LDS

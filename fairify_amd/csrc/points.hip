@@ -28,6 +28,7 @@
 struct PointCfg {
   int w_lds[FA_MAX_LAYERS];   // LDS float offset of W_l in MFMA operand order
   int b_lds[FA_MAX_LAYERS];
+  int bp_lds[FA_MAX_LAYERS];  // the layer's biases again, zero padded to whole 16-neuron tiles (16-byte aligned)
 };
 
 template <int TM>
@@ -39,7 +40,7 @@ __device__ __forceinline__ void fa_point_layer(const NetDesc& net, const BoundAr
   const int n_in = net.dims[l], n_out = net.dims[l + 1];
   const int tin = (n_in + 15) >> 4, tout = (n_out + 15) >> 4;
   const float* sw = smem + cfg.w_lds[l];
-  const float* sb = smem + cfg.b_lds[l];
+  const float* sbp = smem + cfg.bp_lds[l];
   const bool last = l == net.n_layers - 1;
   const float gg = net.g_fwd[l];
   const float gi = net.g_one;
@@ -47,9 +48,29 @@ __device__ __forceinline__ void fa_point_layer(const NetDesc& net, const BoundAr
   const int noff = net.neuron_off[l];
   const int p = p0 + col;
   const bool pv = p < a.R;
+  // forced-zero flags of this point's hidden layer l (per point, or per the point's partition); which
+  // of the two masks is in use is wave-uniform and decided here, not per accumulator register
+  const bool masked = !last && (a.dead_in || a.dead_part);
+  const uint8_t* drow = nullptr;
+  if (masked && pv) {
+    if (a.dead_in) drow = a.dead_in + (size_t)p * net.n_hidden + noff;
+    else drow = a.dead_part + (size_t)a.node_part[a.part_mod ? p % a.part_mod : p] * net.n_hidden + noff;
+  }
 #pragma unroll
   for (int jt = 0; jt < TM; ++jt) {
     if (jt >= tout) break;
+    // the lane's four biases of this tile, read ahead of the chains (their MFMAs cover the LDS wait)
+    // with one unguarded 16-byte read of the zero-padded copy (a padded neuron's bias is 0)
+    const float4 b4 = *reinterpret_cast<const float4*>(sbp + 16 * jt + 4 * grp);
+    const float bl[4] = {b4.x, b4.y, b4.z, b4.w};
+    bool forced[4] = {false, false, false, false};
+    if (masked) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int j = 16 * jt + 4 * grp + i;
+        forced[i] = drow && j < n_out && drow[j] != 0;
+      }
+    }
     f32x4 Z = {0.f, 0.f, 0.f, 0.f}, Q = {0.f, 0.f, 0.f, 0.f};
     const float4* wq = reinterpret_cast<const float4*>(sw) + (size_t)jt * tin * 64 + lane;
 #pragma unroll
@@ -67,9 +88,11 @@ __device__ __forceinline__ void fa_point_layer(const NetDesc& net, const BoundAr
     for (int i = 0; i < 4; ++i) {
       const int j = 16 * jt + 4 * grp + i;
       const bool jv = j < n_out;
-      const float b = jv ? sb[j] : 0.f;
+      const float b = bl[i];
       const float z = Z[i] + b;
-      const float d = Q[i] * (1.f + 2.f * gg) + gg * fabsf(b) + gi * fabsf(z);
+      // explicit fused steps (one rounding each), so that the bounds do not depend on which of the
+      // products the compiler chooses to contract: Q (1 + 2g) + (g|b|), then + g1|z|
+      const float d = fmaf(gi, fabsf(z), fmaf(Q[i], 1.f + 2.f * gg, gg * fabsf(b)));
       if (last) {
         if (j == 0 && pv) {
           a.out_lb[p] = z - d;
@@ -77,17 +100,11 @@ __device__ __forceinline__ void fa_point_layer(const NetDesc& net, const BoundAr
         }
         continue;
       }
-      bool forced = false;
-      if (jv && pv) {
-        if (a.dead_in) forced = a.dead_in[(size_t)p * net.n_hidden + noff + j] != 0;
-        else if (a.dead_part)
-          forced = a.dead_part[(size_t)a.node_part[a.part_mod ? p % a.part_mod : p] * net.n_hidden + noff + j] != 0;
-      }
-      const bool zero = !jv || forced || (z + d <= 0.f);
+      const bool zero = !jv || forced[i] || (z + d <= 0.f);
       const float h = zero ? 0.f : fmaxf(z, 0.f);
       const float e = zero ? 0.f : d;
       H2[jt][i] = h;
-      E2[jt][i] = e + gnext * h;       // next layer's error operand: e + g |h|  (h >= 0)
+      E2[jt][i] = fmaf(gnext, h, e);   // next layer's error operand: e + g |h|  (h >= 0), fused
     }
   }
 }
@@ -102,6 +119,11 @@ __global__ void __launch_bounds__(FA_THREADS) __attribute__((amdgpu_waves_per_eu
     const float4* src = reinterpret_cast<const float4*>(a.flat + net.wperm_off);
     float4* dst = reinterpret_cast<float4*>(smem);
     for (int e = tid; e < (net.wperm_floats >> 2); e += FA_THREADS) dst[e] = src[e];
+    for (int l = 0; l < net.n_layers; ++l) {
+      const int n_out = net.dims[l + 1];
+      const float* b = a.flat + net.wperm_off + cfg.b_lds[l];
+      for (int j = tid; j < ((n_out + 15) & ~15); j += FA_THREADS) smem[cfg.bp_lds[l] + j] = j < n_out ? b[j] : 0.f;
+    }
   }
   __syncthreads();
   const int lane = tid & 63, col = lane & 15, grp = lane >> 4;
@@ -181,8 +203,13 @@ extern "C" int fa_point_try_launch(const NetDesc& net, BoundArgs a, hipStream_t 
     off += net.dims[l + 1];
   }
   if (((off + 3) & ~3) != net.wperm_floats) return -1;   // layout mismatch with the pre-permuted block
-  const size_t bytes = (size_t)((off + 3) & ~3) * sizeof(float);
-  if (bytes > 150 * 1024) return 0;
+  if ((size_t)net.wperm_floats * sizeof(float) > 150 * 1024) return 0;
+  off = net.wperm_floats;
+  for (int l = 0; l < net.n_layers; ++l) {
+    cfg.bp_lds[l] = off;
+    off += ((net.dims[l + 1] + 15) / 16) * 16;
+  }
+  const size_t bytes = (size_t)off * sizeof(float);   // <= 150 KB + 16 layers x 10 tiles x 64 B
   static std::mutex mu;
   static std::map<std::pair<const void*, size_t>, int> occ;
   int per_cu = 0;

@@ -188,7 +188,7 @@ __global__ void __launch_bounds__(FA_THREADS) fa_agree_kernel(NetDesc net, RegNe
   float* s_hi = s_lo + n0;
   int* acc = (int*)(s_hi + n0);
   uint8_t* dm = (uint8_t*)(acc + 4);
-  fa_stage_wperm(net, flat, smem, tid, FA_THREADS);
+  fa_stage_wperm(net, cfg, flat, smem, tid, FA_THREADS);
   for (int i = tid; i < n0; i += FA_THREADS) {
     s_lo[i] = lo[(size_t)p * n0 + i];
     s_hi[i] = hi[(size_t)p * n0 + i];

@@ -13,7 +13,8 @@
 struct RegNetCfg {
   int w_lds[FA_MAX_LAYERS];
   int b_lds[FA_MAX_LAYERS];
-  int floats;                 // staged block size (== net.wperm_floats)
+  int bp_lds[FA_MAX_LAYERS];  // the layer's biases again, zero padded to whole 16-neuron tiles (16-byte aligned)
+  int floats;                 // staged LDS floats: the block (net.wperm_floats), then the padded biases
 };
 
 // Host helper: offsets of the permuted block; returns false on a layout mismatch.
@@ -27,8 +28,14 @@ inline bool fa_regnet_cfg(const NetDesc& net, RegNetCfg& cfg) {
     cfg.b_lds[l] = off;
     off += net.dims[l + 1];
   }
-  cfg.floats = (off + 3) & ~3;
-  return cfg.floats == net.wperm_floats;
+  const int block = (off + 3) & ~3;
+  off = block;
+  for (int l = 0; l < net.n_layers; ++l) {
+    cfg.bp_lds[l] = off;
+    off += ((net.dims[l + 1] + 15) / 16) * 16;
+  }
+  cfg.floats = off;
+  return block == net.wperm_floats;
 }
 
 // Largest 16-neuron tile count over all layers (input included): the register tile depth.
@@ -38,12 +45,19 @@ inline int fa_regnet_tm(const NetDesc& net) {
   return tm;
 }
 
-// Stage the permuted W + biases (flat + wperm_off) into LDS with float4 copies (all threads).
-__device__ __forceinline__ void fa_stage_wperm(const NetDesc& net, const float* flat, float* smem, int tid,
-                                               int nthreads) {
+// Stage the permuted W + biases (flat + wperm_off) into LDS with float4 copies (all threads), then
+// the zero-padded per-tile bias copies: a lane reads the four biases of its accumulator registers
+// with one unguarded 16-byte ds_read instead of four guarded 4-byte ones.
+__device__ __forceinline__ void fa_stage_wperm(const NetDesc& net, const RegNetCfg& cfg, const float* flat,
+                                               float* smem, int tid, int nthreads) {
   const float4* src = reinterpret_cast<const float4*>(flat + net.wperm_off);
   float4* dst = reinterpret_cast<float4*>(smem);
   for (int e = tid; e < (net.wperm_floats >> 2); e += nthreads) dst[e] = src[e];
+  for (int l = 0; l < net.n_layers; ++l) {
+    const int n_out = net.dims[l + 1];
+    const float* b = flat + net.wperm_off + cfg.b_lds[l];
+    for (int j = tid; j < ((n_out + 15) & ~15); j += nthreads) smem[cfg.bp_lds[l] + j] = j < n_out ? b[j] : 0.f;
+  }
 }
 
 // One layer: H (inputs of layer l) -> H2 (ReLU outputs; padded neurons 0).  On the last layer
@@ -58,11 +72,18 @@ __device__ __forceinline__ float fa_reg_layer(const NetDesc& net, const RegNetCf
   const int tin = (n_in + 15) >> 4, tout = (n_out + 15) >> 4;
   const float4* sw = reinterpret_cast<const float4*>(sw_all + cfg.w_lds[l]);
   const float* sb = sw_all + cfg.b_lds[l];
+  const float* sbp = sw_all + cfg.bp_lds[l];
   const bool last = l == net.n_layers - 1;
+  const uint8_t* dl = dead ? dead + net.neuron_off[l] : nullptr;   // wave-uniform
   float logit = 0.f;
 #pragma unroll
   for (int jt = 0; jt < TM; ++jt) {
     if (jt >= tout) break;
+    // the lane's four biases of this tile, read ahead of the chain (its MFMAs cover the LDS wait)
+    // and unguarded, from the zero-padded copy.  The bias stays a separate add after the chain: an
+    // accumulator started at it would round differently.
+    const float4 b4 = *reinterpret_cast<const float4*>(sbp + 16 * jt + 4 * grp);
+    const float b[4] = {b4.x, b4.y, b4.z, b4.w};
     f32x4 Z = {0.f, 0.f, 0.f, 0.f};
     const float4* wq = sw + (size_t)jt * tin * 64 + lane;
 #pragma unroll
@@ -78,11 +99,19 @@ __device__ __forceinline__ float fa_reg_layer(const NetDesc& net, const RegNetCf
       if (jt == 0) logit = Z[0] + sb[0];
       continue;
     }
+    if (dl) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int j = 16 * jt + 4 * grp + i;
-      const bool zero = j >= n_out || (dead && dead[net.neuron_off[l] + j]);
-      H2[jt][i] = zero ? 0.f : fmaxf(Z[i] + sb[j], 0.f);
+      for (int i = 0; i < 4; ++i) {
+        const int j = 16 * jt + 4 * grp + i;
+        const bool zero = j >= n_out || dl[j];
+        H2[jt][i] = zero ? 0.f : fmaxf(Z[i] + b[i], 0.f);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int j = 16 * jt + 4 * grp + i;
+        H2[jt][i] = j >= n_out ? 0.f : fmaxf(Z[i] + b[i], 0.f);
+      }
     }
   }
   return logit;

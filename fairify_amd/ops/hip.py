@@ -442,6 +442,19 @@ def _sim_split(P: int, n_samples: int) -> int:
     return max(1, min(tiles, -(-target // P)))
 
 
+# FAIRIFY_SIM_REGCOUNT=0: every network runs the run-time-shape simulation kernel (A/B against the
+# compile-time-shape instances that count activations in registers, csrc/forward.hip); passed per
+# call, parsed once at import like FAIRIFY_SIM_BLOCKS (_SIM_REGCOUNT_ENV = "dynamic": re-read per call)
+_SIM_REGCOUNT = os.environ.get("FAIRIFY_SIM_REGCOUNT", "1").strip() != "0"
+_SIM_REGCOUNT_ENV: Optional[str] = None
+
+
+def _sim_regcount() -> bool:
+    if _SIM_REGCOUNT_ENV is None:
+        return _SIM_REGCOUNT
+    return os.environ.get("FAIRIFY_SIM_REGCOUNT", "1").strip() != "0"
+
+
 def simulate(be, q, lo, hi, pids, n_samples, seed, values, pairs, bisect_pairs, bisect_steps, return_z0=False):
     from ..engine.sim import SimResult, boundary_walk
 
@@ -460,14 +473,17 @@ def simulate(be, q, lo, hi, pids, n_samples, seed, values, pairs, bisect_pairs, 
     found = torch.zeros(P, dtype=torch.uint8, device=dev)
     wx = torch.zeros(P, n0, dtype=torch.float32, device=dev)
     wxp = torch.zeros(P, n0, dtype=torch.float32, device=dev)
-    z0 = torch.empty(P, n_samples, dtype=torch.float32, device=dev) if (bisect_pairs and bisect_steps) else None
+    walk = bool(bisect_pairs and bisect_steps)
+    z0 = torch.empty(P, n_samples, dtype=torch.float32, device=dev) if (walk or return_z0) else None
     if P and n_samples:
         ext().sim(_net(be), be.flat.data_ptr(), lo_c.data_ptr(), hi_c.data_ptr(), pids_c.data_ptr(), P, n_samples,
                   int(seed) & 0xFFFFFFFF, V, list(q.pa_idx), values_c.data_ptr(), Pp, pairs_c.data_ptr(),
                   list(q.ra_idx) if q.relaxed else [], int(q.tau), counts.data_ptr(), found.data_ptr(),
-                  wx.data_ptr(), wxp.data_ptr(), _ptr(z0), _ptr(keys), split, _stream(dev))
+                  wx.data_ptr(), wxp.data_ptr(), _ptr(z0), _ptr(keys), split, int(_sim_regcount()), _stream(dev))
     res = SimResult(counts=counts, found=found.bool(), wit_x=wx, wit_xp=wxp)
-    if z0 is not None:
+    if return_z0:
+        res.z0 = z0
+    if walk:
         boundary_walk(be, q, lo_c, hi_c, pids_c, n_samples, seed, values_c, pairs_c, res, z0, bisect_pairs,
                       bisect_steps)
     return res

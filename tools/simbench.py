@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Micro-benchmark of the simulation kernel (fa_sim_kernel, K3+K8): ``simulate`` on --partitions
 partitions of every AC model, one stream, median of --reps timed launches after a warm launch.
-Prints one JSON line per model plus a checksum of the activation counts / flip keys, so two
+Prints one JSON line per model (median, fastest and slowest rep) plus a checksum of the activation counts / flip keys, so two
 builds can be compared for both speed and bitwise-identical results.
 
     python tools/simbench.py --partitions 8192 --reps 5
@@ -61,8 +61,9 @@ def main():
             torch.cuda.synchronize()
             ts.append(time.perf_counter() - t0)
         h = hashlib.sha1(res.counts.cpu().numpy().tobytes() + res.found.cpu().numpy().tobytes()).hexdigest()[:12]
-        print(json.dumps({"model": name, "ms": round(1e3 * float(np.median(ts)), 3), "found": int(res.found.sum()),
-                          "hash": h}), flush=True)
+        print(json.dumps({"model": name, "ms": round(1e3 * float(np.median(ts)), 3),
+                          "min_ms": round(1e3 * min(ts), 3), "max_ms": round(1e3 * max(ts), 3),
+                          "found": int(res.found.sum()), "hash": h}), flush=True)
 
 
 if __name__ == "__main__":
