@@ -5,6 +5,7 @@
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m fairify_amd.cli verify --preset stress/AC ...
     python -m fairify_amd.cli zoo [--import-dir /path/to/models]
     python -m fairify_amd.cli analyze --preset experiment/AC-3 --model AC-3 --fairer AC-3 ...
+    python -m fairify_amd.cli measure --preset src/GC-age --model GC-1 --results results/gc --out results/gc-rate
     python -m fairify_amd.cli repair --model AC-3 --counterexamples results/ac3/counterexamples.csv ...
     python -m fairify_amd.cli export-cex --preset src/AC-sex --model AC-3 --results results/ac
 
@@ -97,6 +98,15 @@ def cmd_analyze(args):
     out = analyze_model(args.preset, args.model, fairer=args.fairer, results=args.results, weights=args.weights,
                         seed=args.seed, out_dir=args.out, device=_device(args.device),
                         causal_samples=args.causal_max)
+    print(json.dumps(out, indent=2, default=float))
+
+
+def cmd_measure(args):
+    from .analysis.rate import measure_preset
+
+    out = measure_preset(args.preset, args.model, results=args.results, n_samples=args.samples, seed=args.seed,
+                         max_partitions=args.max_partitions, check_unsat=args.check_unsat, weights=args.weights,
+                         device=_device(args.device), out_dir=args.out)
     print(json.dumps(out, indent=2, default=float))
 
 
@@ -241,6 +251,21 @@ def main(argv=None):
     a.add_argument("--causal-max", type=int, default=1000)
     a.add_argument("--device", default=None)
     a.set_defaults(fn=cmd_analyze)
+
+    ms = sub.add_parser("measure", help="per-partition discrimination rates + stratified domain-wide estimate")
+    ms.add_argument("--preset", required=True)
+    ms.add_argument("--model", required=True)
+    ms.add_argument("--results", default=None,
+                    help="results dir of a verify run: UNSAT partitions count as rate 0 and are not sampled")
+    ms.add_argument("--samples", type=int, default=1000, help="profiles per partition")
+    ms.add_argument("--seed", type=int, default=0)
+    ms.add_argument("--max-partitions", type=int, default=None)
+    ms.add_argument("--check-unsat", action="store_true",
+                    help="sample the UNSAT partitions too; an exact flip inside one is a prover bug (SoundnessError)")
+    ms.add_argument("--weights", default="zoo")
+    ms.add_argument("--device", default=None)
+    ms.add_argument("--out", default=None, help="directory for rate.csv / rate.json")
+    ms.set_defaults(fn=cmd_measure)
 
     r = sub.add_parser("repair", help="bias localisation + masked fine-tune / counterexample retraining")
     r.add_argument("--model", required=True)

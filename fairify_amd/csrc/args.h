@@ -506,3 +506,34 @@ struct BetaPoolArgs {
   int root;
   float* cand_buf; int* cand_count; int cand_cap;  // pinned records (x [n0], x' [n0], partition)
 };
+
+// Discrimination-rate measurement (csrc/rate.hip): n_samples profiles per partition from the
+// simulation stage's hash stream, every profile's x rows (one per PA assignment) against its
+// counterpart rows x' (the x rows, or -- relaxed -- the x rows shifted by every RA offset vector),
+// classified with the rigorous point bounds.
+#define FA_RATE_SLOTS 32    // recorded ambiguous sample indices per partition
+#define FA_RATE_MAX_V 32
+#define FA_RATE_MAX_E 32
+struct RateArgs {
+  const float* flat;
+  const float* lo;          // [P, n0]
+  const float* hi;          // [P, n0]
+  const int64_t* pids;      // [P]
+  int P;
+  int n_samples;
+  uint32_t seed;
+  int V;                    // PA assignments
+  int npa;
+  int pa_idx[FA_MAX_PA];
+  const int64_t* values;    // [V, npa]
+  int Pp;                   // valid ordered pairs
+  const int64_t* pairs;     // [Pp, 2]
+  int nra;                  // 0: PA-only query (the x rows are their own counterparts)
+  int ra_idx[FA_MAX_RA];
+  int tau;
+  int E;                    // (2 tau + 1)^nra offset vectors, row-major over ra_idx (1 when nra == 0)
+  int* flips;               // [P] certain profiles                     (zero-initialised by the caller)
+  int* amb;                 // [P] ambiguous profiles                   (zero-initialised by the caller)
+  int* amb_idx;             // [P, FA_RATE_SLOTS] their sample indices, any order; complete iff amb <= slots
+  int split;                // workgroups per partition (64-profile passes strided over them)
+};

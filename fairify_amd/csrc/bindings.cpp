@@ -24,6 +24,7 @@ extern "C" int fa_point_try_launch(const NetDesc& net, BoundArgs a, hipStream_t 
 extern "C" int fa_forward_launch(const NetDesc& net, FwdArgs a, hipStream_t stream);
 extern "C" int fa_sim_launch(const NetDesc& net, SimArgs a, hipStream_t stream);
 extern "C" int fa_sim_shaped(const NetDesc& net);
+extern "C" int fa_rate_launch(const NetDesc& net, RateArgs a, hipStream_t stream);
 extern "C" int fa_ascent_launch(const NetDesc& net, AscentArgs a, hipStream_t stream);
 extern "C" int fa_certify_launch(CertArgs a, hipStream_t stream);
 extern "C" int fa_falsify_launch(const NetDesc& net, FalsifyArgs a, hipStream_t stream);
@@ -342,6 +343,39 @@ PYBIND11_MODULE(_C, m) {
     ckl(fa_sim_launch(net.d, a, (hipStream_t)stream), "sim");
   });
   m.def("sim_shaped", [](const Net& net) { return fa_sim_shaped(net.d) != 0; });
+
+  // discrimination-rate counts (csrc/rate.hip); flips / amb zero-initialised by the caller
+  m.def("rate", [](const Net& net, uintptr_t flat, uintptr_t lo, uintptr_t hi, uintptr_t pids, int Pn, int n_samples,
+                   uint32_t seed, int V, const std::vector<int>& pa, uintptr_t values, int Pp, uintptr_t pairs,
+                   const std::vector<int>& ra, int tau, int E, uintptr_t flips, uintptr_t amb, uintptr_t amb_idx,
+                   int split, uintptr_t stream) {
+    if (pa.size() > FA_MAX_PA || ra.size() > FA_MAX_RA) throw std::invalid_argument("too many PA/RA dims");
+    RateArgs a{};
+    a.flat = P<const float>(flat);
+    a.lo = P<const float>(lo);
+    a.hi = P<const float>(hi);
+    a.pids = P<const int64_t>(pids);
+    a.P = Pn;
+    a.n_samples = n_samples;
+    a.seed = seed;
+    a.V = V;
+    a.npa = (int)pa.size();
+    for (size_t i = 0; i < pa.size(); ++i) a.pa_idx[i] = pa[i];
+    a.values = P<const int64_t>(values);
+    a.Pp = Pp;
+    a.pairs = P<const int64_t>(pairs);
+    a.nra = (int)ra.size();
+    for (size_t i = 0; i < ra.size(); ++i) a.ra_idx[i] = ra[i];
+    a.tau = tau;
+    a.E = E;
+    a.flips = P<int>(flips);
+    a.amb = P<int>(amb);
+    a.amb_idx = P<int>(amb_idx);
+    a.split = split;
+    const int rc = fa_rate_launch(net.d, a, (hipStream_t)stream);
+    if (rc == -3) throw std::invalid_argument("rate: shape not covered (layer > 160, inputs > 32, V > 32 or E > 32)");
+    ckl(rc, "rate");
+  });
 
   // returns false if the partition's candidate rows do not fit in LDS (caller keeps PyTorch)
   m.def("ascent", [](const Net& net, uintptr_t flat, uintptr_t lo, uintptr_t hi, uintptr_t x0, uintptr_t f0,

@@ -66,6 +66,14 @@ __device__ __forceinline__ uint32_t fa_rng(uint32_t seed, int64_t pid, int64_t s
   return h;
 }
 
+// ops/reference.py:sample_points: coordinate d of sample s of partition pid, uniform on the integers
+// lo..hi (the simulation stage's stream; csrc/forward.hip, csrc/rate.hip)
+__device__ __forceinline__ float fa_sample_coord(uint32_t seed, int64_t pid, int s, int d, float lo, float hi) {
+  const uint32_t h = fa_rng(seed, pid, s, d);
+  const uint32_t w = (uint32_t)(hi - lo) + 1u;
+  return lo + (float)(h % w);
+}
+
 // One v_mfma_f32_16x16x4_f32: exact f32 fma chain.  Lane l supplies A[l&15][l>>4] and
 // B[l>>4][l&15]; D reg i is row (l>>4)*4+i, column l&15.
 __device__ __forceinline__ f32x4 fa_mfma4(float a, float b, f32x4 c) {

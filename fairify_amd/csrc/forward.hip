@@ -126,12 +126,6 @@ extern "C" int fa_forward_launch(const NetDesc& net, FwdArgs a, hipStream_t stre
 
 
 
-__device__ __forceinline__ float fa_sample_coord(uint32_t seed, int64_t pid, int s, int d, float lo, float hi) {
-  const uint32_t h = fa_rng(seed, pid, s, d);
-  const uint32_t w = (uint32_t)(hi - lo) + 1u;
-  return lo + (float)(h % w);
-}
-
 // Witness of the first strict flip `key` = sample * Pp + pair of partition p (threads of one block).
 __device__ void fa_sim_witness(const SimArgs& a, int n0, int p, int64_t pid, int key, const float* lo,
                                const float* hi) {

@@ -489,6 +489,72 @@ def simulate(be, q, lo, hi, pids, n_samples, seed, values, pairs, bisect_pairs, 
     return res
 
 
+_RATE_BLOCKS = 1024      # workgroups a short partition list is spread over (4 per CU)
+_RATE_EMPTY = 0x7FFFFFFF
+
+
+def rate_split_max(n_samples: int) -> int:
+    """Largest workgroups-per-partition value of ``fa_rate_kernel``: one per 64-profile pass."""
+    return max(1, (n_samples + 63) // 64)
+
+
+def _rate_split(P: int, n_samples: int) -> int:
+    if not P or P >= _RATE_BLOCKS:
+        return 1
+    return max(1, min(rate_split_max(n_samples), _RATE_BLOCKS // P))
+
+
+def rate_counts(be, q, lo, hi, pids, n_samples, seed, values, pairs, split: Optional[int] = None):
+    """Discrimination-rate counts of ``P`` partitions in one fused launch (``fa_rate_kernel``,
+    definitions in ops/rate.py): (certain profiles [P], ambiguous profiles [P], ambiguous sample
+    indices [P, 32]) int32.  An index row is sorted ascending and padded with INT32_MAX; the row of
+    a partition with more than 32 ambiguous profiles is not trusted and returned all padding.
+    ``split``: workgroups per partition (default: by the list length); every value gives the same
+    outputs."""
+    from .rate import AMB_SLOTS, MAX_OFFSETS, offset_vectors
+
+    P, n0 = lo.shape
+    dev = lo.device
+    if n0 != be.n0:
+        raise ValueError(f"lo: expected [P, {be.n0}], got {tuple(lo.shape)}")
+    lo_c = _c(lo, torch.float32, (P, n0), "lo")
+    hi_c = _c(hi, torch.float32, (P, n0), "hi")
+    pids_c = _c(pids, torch.int64, (P,), "pids")
+    npa = len(q.pa_idx)
+    if values.dim() != 2 or values.shape[1] != npa:
+        raise ValueError(f"values: expected [V, {npa}], got {tuple(values.shape)}")
+    V = int(values.shape[0])
+    Pp = int(pairs.shape[0])
+    values_c = _c(values, torch.int64, (V, npa), "values")
+    pairs_c = _c(pairs, torch.int64, (Pp, 2), "pairs")
+    if not 1 <= V <= 32:
+        raise ValueError(f"rate: {V} PA assignments, the kernel covers 1..32")
+    if Pp and (int(pairs_c.min()) < 0 or int(pairs_c.max()) >= V):
+        raise ValueError("pairs: index outside [0, V)")
+    E = int(offset_vectors(q).shape[0])                    # raises over MAX_OFFSETS
+    assert E <= MAX_OFFSETS
+    n_samples = int(n_samples)
+    if n_samples < 0 or n_samples >= _RATE_EMPTY:
+        raise ValueError(f"rate: bad sample count {n_samples}")
+    if max([be.n0] + list(be.widths)) > 160 or be.n0 > 32:
+        raise ValueError("rate: the kernel covers layers up to 160 wide and up to 32 inputs")
+    if split is None:
+        split = _rate_split(P, n_samples)
+    if not 1 <= int(split) <= rate_split_max(n_samples):
+        raise ValueError(f"rate: split {split} outside 1..{rate_split_max(n_samples)}")
+    flips = torch.zeros(P, dtype=torch.int32, device=dev)
+    amb = torch.zeros(P, dtype=torch.int32, device=dev)
+    idx = torch.full((P, AMB_SLOTS), _RATE_EMPTY, dtype=torch.int32, device=dev)
+    if P and n_samples:
+        ext().rate(_net(be), be.flat.data_ptr(), lo_c.data_ptr(), hi_c.data_ptr(), pids_c.data_ptr(), P, n_samples,
+                   int(seed) & 0xFFFFFFFF, V, list(q.pa_idx), values_c.data_ptr(), Pp, pairs_c.data_ptr(),
+                   list(q.ra_idx) if q.relaxed else [], int(q.tau) if q.relaxed else 0, E, flips.data_ptr(),
+                   amb.data_ptr(), idx.data_ptr(), int(split), _stream(dev))
+        # slots are taken in atomic order: canonical form, and nothing from an overflowed row
+        idx = idx.masked_fill((amb > AMB_SLOTS)[:, None], _RATE_EMPTY).sort(dim=1).values
+    return flips, amb, idx
+
+
 def ascent(be, q, lo, hi, x0, f0, q0, iters, values, pairs, free_dims):
     """Lattice coordinate ascent of the residual falsifier in one launch (``fa_ascent_kernel``).
 
