@@ -3,19 +3,26 @@
 // Tensors cross the boundary as raw device pointers (Python ints from Tensor.data_ptr()) plus
 // the caller's HIP stream (torch.cuda.current_stream().cuda_stream), so the extension has no
 // dependency on the torch C++ headers and launches onto whatever stream torch is using.
+//
+// A binding that fills one of the larger args.h structs takes (net, **keywords): every key is the
+// struct field's name (plus `stream`), read through Kw (kwargs.h) by the family's filler below, so a
+// field is named once here and once in ops/hip.py and a missing or unknown key raises TypeError before
+// any launch.  Bindings that pass up to 14 scalars straight to a launcher or into a small struct of
+// their own (forward, decode, pack_masks, knn, actdiff, prune_masks, heuristic, agree, trace_marker)
+// stay positional: nothing there is repeated.
 #include <hip/hip_runtime.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <cstdint>
 #include <stdexcept>
 #include <vector>
 
+#include "kwargs.h"
 #include "runtime_host.h"
-
-namespace py = pybind11;
 
 extern "C" int fa_bounds_launch(const NetDesc& net, BoundArgs args, hipStream_t stream);
 extern "C" int fa_crown_phase_launch(const NetDesc& net, CrownPhaseArgs a, hipStream_t stream);
@@ -131,6 +138,137 @@ void register_csv(py::module& m);
 
 using fa_rt::ckl;
 
+// ---- fillers: one per struct family, the keys are the args.h field names ---------------------------
+// the stream key, read last: every key the caller passed must have been read by then
+static hipStream_t finish(Kw& k) {
+  const hipStream_t s = reinterpret_cast<hipStream_t>(k.u64("stream"));
+  k.done();
+  return s;
+}
+
+// an index list (pa -> npa / pa_idx, ra -> nra / ra_idx, free -> nfree / free_idx); returns its length
+static int dims(Kw& k, const char* key, int* idx, size_t cap, const char* too_many) {
+  const std::vector<int> v = k.ints(key);
+  if (v.size() > cap) throw std::invalid_argument(too_many);
+  std::copy(v.begin(), v.end(), idx);
+  return (int)v.size();
+}
+
+// The block BoundArgs and CrownPhaseArgs share.  `req`: the pointer groups the entry cannot run without
+// (the others may be left out: nullptr); lo / hi: the keys of the row boxes.
+enum { OUT = 1, FORMS = 2, LAYERS = 4 };
+template <typename A>
+static A row_args(Kw& k, int req, const char* lo = "lo", const char* hi = "hi") {
+  auto p = [&](const char* key, int group) { return (req & group) ? k.need<float>(key) : k.ptr<float>(key); };
+  A a{};
+  a.flat = k.need<const float>("flat");
+  a.lo = k.need<const float>(lo);
+  a.hi = k.need<const float>(hi);
+  a.R = k.i("R");
+  a.out_lb = p("out_lb", OUT);
+  a.out_ub = p("out_ub", OUT);
+  a.Lc = p("Lc", FORMS); a.L0 = p("L0", FORMS); a.Le = p("Le", FORMS);
+  a.Uc = p("Uc", FORMS); a.U0 = p("U0", FORMS); a.Ue = p("Ue", FORMS);
+  a.layer_lb = p("layer_lb", LAYERS);
+  a.layer_ub = p("layer_ub", LAYERS);
+  return a;
+}
+static BoundArgs bound_args(Kw& k, int req, const char* lo = "lo", const char* hi = "hi") {
+  BoundArgs a = row_args<BoundArgs>(k, req, lo, hi);
+  a.dead_in = k.ptr<const uint8_t>("dead_in");
+  return a;
+}
+
+// The query block SimArgs, RateArgs, FalsifyArgs and AscentArgs share ...
+template <typename A>
+static void fill_query(A& a, Kw& k, const char* too_many) {
+  a.flat = k.need<const float>("flat");
+  a.lo = k.need<const float>("lo");
+  a.hi = k.need<const float>("hi");
+  a.P = k.i("P");
+  a.V = k.i("V");
+  a.npa = dims(k, "pa", a.pa_idx, FA_MAX_PA, too_many);
+  a.values = k.ptr<const int64_t>("values");
+  a.Pp = k.i("Pp");
+  a.pairs = k.ptr<const int64_t>("pairs");
+}
+// ... the sample stream and the RA offsets of the three that draw their points (not AscentArgs) ...
+template <typename A>
+static void fill_samples(A& a, Kw& k, const char* too_many) {
+  a.pids = k.need<const int64_t>("pids");
+  a.n_samples = k.i("n_samples");
+  a.seed = (uint32_t)k.u64("seed");
+  a.nra = dims(k, "ra", a.ra_idx, FA_MAX_RA, too_many);
+  a.tau = k.i("tau");
+}
+// ... and the witness outputs with the free dims of the two that run the lattice ascent
+template <typename A>
+static void fill_ascent(A& a, Kw& k, const char* too_many) {
+  a.K = k.i("K");
+  a.iters = k.i("iters");
+  a.nfree = dims(k, "free", a.free_idx, 64, too_many);
+  a.found = k.need<uint8_t>("found");
+  a.wit_x = k.need<float>("wit_x");
+  a.wit_xp = k.need<float>("wit_xp");
+}
+
+// One beta level (BetaArgs; beta_level and the batched entry points share it).  `flags`: bit 0 stall,
+// bits 1-2 the primal-gap weights, bit 3 the infeasibility pass (ops/hip.py:beta_flags).
+static BetaArgs beta_args(const Net& net, Kw& k) {
+  BetaArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.flat = k.need<const float>("flat");
+  a.wt = k.ptr<const float>("wt");
+  a.R = k.i("R");
+  a.npa = dims(k, "pa", a.pa_idx, FA_MAX_PA, "beta_level: too many PA dims");
+  for (int q = 0; q < a.npa; ++q)
+    if (a.pa_idx[q] < 0 || a.pa_idx[q] >= net.d.dims[0] || (q && a.pa_idx[q] <= a.pa_idx[q - 1]))
+      throw std::invalid_argument("beta_level: PA dims must be increasing input indices");
+  a.lo = k.need<const float>("lo");
+  a.hi = k.need<const float>("hi");
+  a.va = k.need<const float>("va");
+  a.vb = k.need<const float>("vb");
+  a.LBA = k.need<const float>("LBA");
+  a.UBA = k.need<const float>("UBA");
+  a.LBB = k.need<const float>("LBB");
+  a.UBB = k.need<const float>("UBB");
+  a.phA = k.need<const int8_t>("phA");
+  a.phB = k.need<const int8_t>("phB");
+  a.par = k.need<float>("par");
+  a.t = k.need<float>("t");
+  a.scratch = k.need<float>("scratch");
+  a.iters = k.i("iters");
+  a.lr_a = k.f("lr_a");
+  a.lr_b = k.f("lr_b");
+  a.lr_t = k.f("lr_t");
+  a.decay = k.f("decay");
+  a.lookahead = k.i("lookahead", 0);
+  a.beta_pos = k.i("beta_pos", 1);
+  const int flags = k.i("flags", 0);
+  a.stall = flags & 1;
+  a.pgap = (flags >> 1) & 3;
+  a.feas = (flags >> 3) & 1;      // scratch [R, 16, NH]
+  a.bound = k.ptr<double>("bound");
+  a.split = k.ptr<int>("split");
+  a.xstar = k.ptr<float>("xstar");
+  a.binit = k.ptr<float>("binit");
+  a.ramask = k.u64("ramask", 0);
+  a.plo = k.ptr<const float>("plo");
+  a.phi = k.ptr<const float>("phi");
+  a.xpstar = k.ptr<float>("xpstar");
+  a.gtie = k.ptr<float>("gtie");
+  a.tau = k.f("tau", 0.f);
+  a.osg = k.ptr<const int8_t>("osg");
+  a.pgsum = k.ptr<const float>("pgsum");
+  a.pgn = k.ptr<const float>("pgn");
+  a.fpar = k.ptr<float>("fpar");
+  a.fgt = k.ptr<float>("fgt");
+  a.fval = k.ptr<double>("fval");
+  if ((net.d.dims[0] < 64 && (a.ramask >> net.d.dims[0])) || (a.ramask && (!a.plo || !a.phi)))
+    throw std::invalid_argument("beta_level: RA mask beyond the inputs or no x' box");
+  return a;
+}
+
 PYBIND11_MODULE(_C, m) {
   m.doc() = "fairify_amd CDNA4 (gfx950) kernels";
   py::class_<Net>(m, "Net")
@@ -143,58 +281,29 @@ PYBIND11_MODULE(_C, m) {
       .def_property_readonly("n_hidden", [](const Net& n) { return n.d.n_hidden; })
       .def_property_readonly("n_neurons", [](const Net& n) { return n.d.n_neurons; });
 
-  m.def("bounds", [](const Net& net, uintptr_t flat, uintptr_t lo, uintptr_t hi, uintptr_t dead_in, int R,
-                     int symbolic, uintptr_t out_lb, uintptr_t out_ub, uintptr_t Lc, uintptr_t L0, uintptr_t Le,
-                     uintptr_t Uc, uintptr_t U0, uintptr_t Ue, uintptr_t layer_lb, uintptr_t layer_ub,
-                     uintptr_t dead_out, int G, uintptr_t stream, unsigned long long fold, uintptr_t phase_in,
-                     uintptr_t infeas) {
-    NetDesc d = net.d;
-    BoundArgs a{};
-    a.flat = P<const float>(flat);
-    a.lo = P<const float>(lo);
-    a.hi = P<const float>(hi);
-    a.dead_in = P<const uint8_t>(dead_in);
-    a.R = R;
+  m.def("bounds", [](const Net& net, py::kwargs kw) {
+    Kw k("bounds", kw);
+    const int symbolic = k.i("symbolic");
+    BoundArgs a = bound_args(k, symbolic ? OUT | FORMS : OUT);
     a.symbolic = symbolic;
-    a.G = G;
-    a.out_lb = P<float>(out_lb);
-    a.out_ub = P<float>(out_ub);
-    a.Lc = P<float>(Lc); a.L0 = P<float>(L0); a.Le = P<float>(Le);
-    a.Uc = P<float>(Uc); a.U0 = P<float>(U0); a.Ue = P<float>(Ue);
-    a.layer_lb = P<float>(layer_lb);
-    a.layer_ub = P<float>(layer_ub);
-    a.dead_out = P<uint8_t>(dead_out);
-    a.fold = fold;
-    a.phase_in = P<const int8_t>(phase_in);
-    a.infeas = P<uint8_t>(infeas);
-    ckl(fa_bounds_launch(d, a, (hipStream_t)stream), "bounds");
-  }, py::arg("net"), py::arg("flat"), py::arg("lo"), py::arg("hi"), py::arg("dead_in"), py::arg("R"),
-     py::arg("symbolic"), py::arg("out_lb"), py::arg("out_ub"), py::arg("Lc"), py::arg("L0"), py::arg("Le"),
-     py::arg("Uc"), py::arg("U0"), py::arg("Ue"), py::arg("layer_lb"), py::arg("layer_ub"), py::arg("dead_out"),
-     py::arg("G"), py::arg("stream"), py::arg("fold") = 0ull, py::arg("phase_in") = 0, py::arg("infeas") = 0);
+    a.G = k.i("G", 0);
+    a.dead_out = k.ptr<uint8_t>("dead_out");
+    a.fold = k.u64("fold", 0);
+    a.phase_in = k.ptr<const int8_t>("phase_in");
+    a.infeas = k.ptr<uint8_t>("infeas");
+    ckl(fa_bounds_launch(net.d, a, finish(k)), "bounds");
+  });
 
   // ReLU-phase backward bounds (relu.hip), refining a preceding phase-aware `bounds` call in place
-  m.def("crown_phase", [](const Net& net, uintptr_t flat, uintptr_t lo, uintptr_t hi, int R, uintptr_t phase,
-                          uintptr_t layer_lb, uintptr_t layer_ub, uintptr_t infeas, uintptr_t out_lb, uintptr_t out_ub,
-                          uintptr_t Lc, uintptr_t L0, uintptr_t Le, uintptr_t Uc, uintptr_t U0, uintptr_t Ue,
-                          uintptr_t split, uintptr_t score, uintptr_t low, uintptr_t stream) {
-    CrownPhaseArgs a{};
-    a.flat = P<const float>(flat);
-    a.lo = P<const float>(lo);
-    a.hi = P<const float>(hi);
-    a.R = R;
-    a.phase = P<const int8_t>(phase);
-    a.layer_lb = P<const float>(layer_lb);
-    a.layer_ub = P<const float>(layer_ub);
-    a.infeas = P<const uint8_t>(infeas);
-    a.out_lb = P<float>(out_lb);
-    a.out_ub = P<float>(out_ub);
-    a.Lc = P<float>(Lc); a.L0 = P<float>(L0); a.Le = P<float>(Le);
-    a.Uc = P<float>(Uc); a.U0 = P<float>(U0); a.Ue = P<float>(Ue);
-    a.split = P<int>(split);
-    a.score = P<float>(score);
-    a.low = P<float>(low);
-    const int rc = fa_crown_phase_launch(net.d, a, (hipStream_t)stream);
+  m.def("crown_phase", [](const Net& net, py::kwargs kw) {
+    Kw k("crown_phase", kw);
+    CrownPhaseArgs a = row_args<CrownPhaseArgs>(k, OUT | FORMS | LAYERS);
+    a.phase = k.ptr<const int8_t>("phase");
+    a.infeas = k.ptr<const uint8_t>("infeas");
+    a.split = k.need<int>("split");
+    a.score = k.need<float>("score");
+    a.low = k.ptr<float>("low");
+    const int rc = fa_crown_phase_launch(net.d, a, finish(k));
     if (rc != 0) throw std::runtime_error("crown_phase launch failed, code " + std::to_string(rc));
   });
 
@@ -202,100 +311,51 @@ PYBIND11_MODULE(_C, m) {
   m.def("relu_fits", [](const Net& net) { return fa_crown_phase_bytes(net.d) > 0; });
 
   // backward output bounds refining forms/out bounds written by a preceding `bounds` call
-  m.def("crown", [](const Net& net, uintptr_t flat, uintptr_t lo, uintptr_t hi, uintptr_t dead_in, int R,
-                    uintptr_t out_lb, uintptr_t out_ub, uintptr_t Lc, uintptr_t L0, uintptr_t Le, uintptr_t Uc,
-                    uintptr_t U0, uintptr_t Ue, uintptr_t layer_lb, uintptr_t layer_ub, uintptr_t stream) {
-    BoundArgs a{};
-    a.flat = P<const float>(flat);
-    a.lo = P<const float>(lo);
-    a.hi = P<const float>(hi);
-    a.dead_in = P<const uint8_t>(dead_in);
-    a.R = R;
-    a.out_lb = P<float>(out_lb);
-    a.out_ub = P<float>(out_ub);
-    a.Lc = P<float>(Lc); a.L0 = P<float>(L0); a.Le = P<float>(Le);
-    a.Uc = P<float>(Uc); a.U0 = P<float>(U0); a.Ue = P<float>(Ue);
-    a.layer_lb = P<float>(layer_lb);
-    a.layer_ub = P<float>(layer_ub);
-    ckl(fa_crown_launch(net.d, a, (hipStream_t)stream), "crown");
+  m.def("crown", [](const Net& net, py::kwargs kw) {
+    Kw k("crown", kw);
+    const BoundArgs a = bound_args(k, OUT | FORMS | LAYERS);
+    ckl(fa_crown_launch(net.d, a, finish(k)), "crown");
   });
 
-  // back-substituted hidden-layer bounds (refine.hip), tightening layer_lb / layer_ub of a preceding
-  // symbolic `bounds` call in place; returns the launch code (0 done, -1 shape not supported)
-  m.def("refine", [](const Net& net, uintptr_t flat, uintptr_t lo, uintptr_t hi, uintptr_t dead_in, int R,
-                     uintptr_t layer_lb, uintptr_t layer_ub, uintptr_t stream, uintptr_t phase, uintptr_t infeas) {
-    BoundArgs a{};
-    a.flat = P<const float>(flat);
-    a.lo = P<const float>(lo);
-    a.hi = P<const float>(hi);
-    a.dead_in = P<const uint8_t>(dead_in);
-    a.R = R;
-    a.layer_lb = P<float>(layer_lb);
-    a.layer_ub = P<float>(layer_ub);
-    a.phase_in = P<const int8_t>(phase);   // ReLU-phase rows [R, n_hidden] (+1 / -1 fixed, 0 free)
-    a.infeas = P<uint8_t>(infeas);         // [R] set to 1 where a refined bound contradicts a phase
-    const int rc = fa_refine_launch(net.d, a, (hipStream_t)stream);
+  // The three refine.hip entries return the launch code (0 done, -1 shape not supported).
+  // refine: back-substituted hidden-layer bounds, tightening layer_lb / layer_ub of a preceding symbolic
+  // `bounds` call in place
+  m.def("refine", [](const Net& net, py::kwargs kw) {
+    Kw k("refine", kw);
+    BoundArgs a = bound_args(k, LAYERS);
+    a.phase_in = k.ptr<const int8_t>("phase_in");   // ReLU-phase rows [R, n_hidden] (+1 / -1 fixed, 0 free)
+    a.infeas = k.ptr<uint8_t>("infeas");            // [R] set to 1 where a refined bound contradicts a phase
+    const int rc = fa_refine_launch(net.d, a, finish(k));
     if (rc < -1) throw std::runtime_error("refine launch failed, code " + std::to_string(rc));
     return rc;
-  }, py::arg("net"), py::arg("flat"), py::arg("lo"), py::arg("hi"), py::arg("dead_in"), py::arg("R"),
-     py::arg("layer_lb"), py::arg("layer_ub"), py::arg("stream"), py::arg("phase") = 0, py::arg("infeas") = 0);
-
+  });
   // refined hidden-layer bounds + the logit's backward pass in one launch (what the BaB runtime runs
   // for BaBConfig.refine level 1), tightening a preceding symbolic `bounds` call in place
-  m.def("refine_crown", [](const Net& net, uintptr_t flat, uintptr_t lo, uintptr_t hi, uintptr_t dead_in, int R,
-                           uintptr_t out_lb, uintptr_t out_ub, uintptr_t Lc, uintptr_t L0, uintptr_t Le, uintptr_t Uc,
-                           uintptr_t U0, uintptr_t Ue, uintptr_t layer_lb, uintptr_t layer_ub, uintptr_t stream) {
-    BoundArgs a{};
-    a.flat = P<const float>(flat);
-    a.lo = P<const float>(lo);
-    a.hi = P<const float>(hi);
-    a.dead_in = P<const uint8_t>(dead_in);
-    a.R = R;
-    a.out_lb = P<float>(out_lb); a.out_ub = P<float>(out_ub);
-    a.Lc = P<float>(Lc); a.L0 = P<float>(L0); a.Le = P<float>(Le);
-    a.Uc = P<float>(Uc); a.U0 = P<float>(U0); a.Ue = P<float>(Ue);
-    a.layer_lb = P<float>(layer_lb);
-    a.layer_ub = P<float>(layer_ub);
-    const int rc = fa_refine_crown_launch(net.d, a, (hipStream_t)stream);
+  m.def("refine_crown", [](const Net& net, py::kwargs kw) {
+    Kw k("refine_crown", kw);
+    const BoundArgs a = bound_args(k, OUT | FORMS | LAYERS);
+    const int rc = fa_refine_crown_launch(net.d, a, finish(k));
     if (rc < -1) throw std::runtime_error("refine_crown launch failed, code " + std::to_string(rc));
     return rc;
   });
-
-  // every neuron's bounds and the logit's forms by back-substitution alone (refine.hip, mode FULL);
-  // layer_lb / layer_ub may be 0.  Returns the launch code (0 done, -1 shape not supported)
-  m.def("backward_bounds", [](const Net& net, uintptr_t flat, uintptr_t lo, uintptr_t hi, uintptr_t dead_in, int R,
-                              uintptr_t out_lb, uintptr_t out_ub, uintptr_t Lc, uintptr_t L0, uintptr_t Le,
-                              uintptr_t Uc, uintptr_t U0, uintptr_t Ue, uintptr_t layer_lb, uintptr_t layer_ub,
-                              uintptr_t stream) {
-    BoundArgs a{};
-    a.flat = P<const float>(flat);
-    a.lo = P<const float>(lo);
-    a.hi = P<const float>(hi);
-    a.dead_in = P<const uint8_t>(dead_in);
-    a.R = R;
-    a.out_lb = P<float>(out_lb); a.out_ub = P<float>(out_ub);
-    a.Lc = P<float>(Lc); a.L0 = P<float>(L0); a.Le = P<float>(Le);
-    a.Uc = P<float>(Uc); a.U0 = P<float>(U0); a.Ue = P<float>(Ue);
-    a.layer_lb = P<float>(layer_lb);
-    a.layer_ub = P<float>(layer_ub);
-    const int rc = fa_backward_launch(net.d, a, (hipStream_t)stream);
+  // every neuron's bounds and the logit's forms by back-substitution alone (mode FULL); layer_lb /
+  // layer_ub may be left out
+  m.def("backward_bounds", [](const Net& net, py::kwargs kw) {
+    Kw k("backward_bounds", kw);
+    const BoundArgs a = bound_args(k, OUT | FORMS);
+    const int rc = fa_backward_launch(net.d, a, finish(k));
     if (rc < -1) throw std::runtime_error("backward_bounds launch failed, code " + std::to_string(rc));
     return rc;
   });
 
-  m.def("point_bounds", [](const Net& net, uintptr_t flat, uintptr_t x, uintptr_t dead_in, int R, uintptr_t out_lb,
-                           uintptr_t out_ub, uintptr_t stream) {
-    BoundArgs a{};
-    a.flat = P<const float>(flat);
-    a.lo = P<const float>(x);
-    a.hi = P<const float>(x);
-    a.dead_in = P<const uint8_t>(dead_in);
-    a.R = R;
-    a.out_lb = P<float>(out_lb);
-    a.out_ub = P<float>(out_ub);
-    int rc = fa_point_try_launch(net.d, a, (hipStream_t)stream);
+  // rows that are points: lo = hi = x; the point kernel, or the interval pass where it does not fit
+  m.def("point_bounds", [](const Net& net, py::kwargs kw) {
+    Kw k("point_bounds", kw);
+    const BoundArgs a = bound_args(k, OUT, "x", "x");
+    const hipStream_t stream = finish(k);
+    const int rc = fa_point_try_launch(net.d, a, stream);
     if (rc < 0) ckl(-rc, "point_bounds");
-    if (rc == 0) ckl(fa_bounds_launch(net.d, a, (hipStream_t)stream), "point_bounds(ibp)");
+    if (rc == 0) ckl(fa_bounds_launch(net.d, a, stream), "point_bounds(ibp)");
   });
 
   m.def("forward", [](const Net& net, uintptr_t flat, uintptr_t x, int B, uintptr_t dead, uintptr_t out,
@@ -309,99 +369,50 @@ PYBIND11_MODULE(_C, m) {
     ckl(fa_forward_launch(net.d, a, (hipStream_t)stream), "forward");
   });
 
-  m.def("sim", [](const Net& net, uintptr_t flat, uintptr_t lo, uintptr_t hi, uintptr_t pids, int Pn, int n_samples,
-                  uint32_t seed, int V, const std::vector<int>& pa, uintptr_t values, int Pp, uintptr_t pairs,
-                  const std::vector<int>& ra, int tau, uintptr_t counts, uintptr_t found, uintptr_t wit_x,
-                  uintptr_t wit_xp, uintptr_t z0, uintptr_t keys, int split, int regcount, uintptr_t stream) {
-    if (pa.size() > FA_MAX_PA || ra.size() > FA_MAX_RA) throw std::invalid_argument("too many PA/RA dims");
-    if (split < 1 || (split > 1 && !keys)) throw std::invalid_argument("sim: split > 1 needs a keys buffer");
+  m.def("sim", [](const Net& net, py::kwargs kw) {
+    Kw k("sim", kw);
     SimArgs a{};
-    a.flat = P<const float>(flat);
-    a.lo = P<const float>(lo);
-    a.hi = P<const float>(hi);
-    a.pids = P<const int64_t>(pids);
-    a.P = Pn;
-    a.n_samples = n_samples;
-    a.seed = seed;
-    a.V = V;
-    a.npa = (int)pa.size();
-    for (size_t i = 0; i < pa.size(); ++i) a.pa_idx[i] = pa[i];
-    a.values = P<const int64_t>(values);
-    a.Pp = Pp;
-    a.pairs = P<const int64_t>(pairs);
-    a.nra = (int)ra.size();
-    for (size_t i = 0; i < ra.size(); ++i) a.ra_idx[i] = ra[i];
-    a.tau = tau;
-    a.counts = P<int>(counts);
-    a.found = P<uint8_t>(found);
-    a.wit_x = P<float>(wit_x);
-    a.wit_xp = P<float>(wit_xp);
-    a.z0 = P<float>(z0);
-    a.keys = P<int>(keys);
-    a.split = split;
-    a.regcount = regcount;
-    ckl(fa_sim_launch(net.d, a, (hipStream_t)stream), "sim");
+    fill_query(a, k, "too many PA/RA dims");
+    fill_samples(a, k, "too many PA/RA dims");
+    a.counts = k.need<int>("counts");
+    a.found = k.need<uint8_t>("found");
+    a.wit_x = k.need<float>("wit_x");
+    a.wit_xp = k.need<float>("wit_xp");
+    a.z0 = k.ptr<float>("z0");
+    a.keys = k.ptr<int>("keys");
+    a.split = k.i("split");
+    a.regcount = k.i("regcount");
+    if (a.split < 1 || (a.split > 1 && !a.keys)) throw std::invalid_argument("sim: split > 1 needs a keys buffer");
+    ckl(fa_sim_launch(net.d, a, finish(k)), "sim");
   });
   m.def("sim_shaped", [](const Net& net) { return fa_sim_shaped(net.d) != 0; });
 
   // discrimination-rate counts (csrc/rate.hip); flips / amb zero-initialised by the caller
-  m.def("rate", [](const Net& net, uintptr_t flat, uintptr_t lo, uintptr_t hi, uintptr_t pids, int Pn, int n_samples,
-                   uint32_t seed, int V, const std::vector<int>& pa, uintptr_t values, int Pp, uintptr_t pairs,
-                   const std::vector<int>& ra, int tau, int E, uintptr_t flips, uintptr_t amb, uintptr_t amb_idx,
-                   int split, uintptr_t stream) {
-    if (pa.size() > FA_MAX_PA || ra.size() > FA_MAX_RA) throw std::invalid_argument("too many PA/RA dims");
+  m.def("rate", [](const Net& net, py::kwargs kw) {
+    Kw k("rate", kw);
     RateArgs a{};
-    a.flat = P<const float>(flat);
-    a.lo = P<const float>(lo);
-    a.hi = P<const float>(hi);
-    a.pids = P<const int64_t>(pids);
-    a.P = Pn;
-    a.n_samples = n_samples;
-    a.seed = seed;
-    a.V = V;
-    a.npa = (int)pa.size();
-    for (size_t i = 0; i < pa.size(); ++i) a.pa_idx[i] = pa[i];
-    a.values = P<const int64_t>(values);
-    a.Pp = Pp;
-    a.pairs = P<const int64_t>(pairs);
-    a.nra = (int)ra.size();
-    for (size_t i = 0; i < ra.size(); ++i) a.ra_idx[i] = ra[i];
-    a.tau = tau;
-    a.E = E;
-    a.flips = P<int>(flips);
-    a.amb = P<int>(amb);
-    a.amb_idx = P<int>(amb_idx);
-    a.split = split;
-    const int rc = fa_rate_launch(net.d, a, (hipStream_t)stream);
+    fill_query(a, k, "too many PA/RA dims");
+    fill_samples(a, k, "too many PA/RA dims");
+    a.E = k.i("E");
+    a.flips = k.need<int>("flips");
+    a.amb = k.need<int>("amb");
+    a.amb_idx = k.need<int>("amb_idx");
+    a.split = k.i("split");
+    const int rc = fa_rate_launch(net.d, a, finish(k));
     if (rc == -3) throw std::invalid_argument("rate: shape not covered (layer > 160, inputs > 32, V > 32 or E > 32)");
     ckl(rc, "rate");
   });
 
   // returns false if the partition's candidate rows do not fit in LDS (caller keeps PyTorch)
-  m.def("ascent", [](const Net& net, uintptr_t flat, uintptr_t lo, uintptr_t hi, uintptr_t x0, uintptr_t f0,
-                     uintptr_t q0, int Pn, int K, int iters, int V, const std::vector<int>& pa, uintptr_t values,
-                     int Pp, uintptr_t pairs, const std::vector<int>& free_dims, uintptr_t found, uintptr_t wit_x,
-                     uintptr_t wit_xp, uintptr_t stream) {
-    if (pa.size() > FA_MAX_PA || free_dims.size() > 64) throw std::invalid_argument("too many PA/free dims");
+  m.def("ascent", [](const Net& net, py::kwargs kw) {
+    Kw k("ascent", kw);
     AscentArgs a{};
-    a.flat = P<const float>(flat);
-    a.lo = P<const float>(lo);
-    a.hi = P<const float>(hi);
-    a.x0 = P<const float>(x0);
-    a.f0 = P<const float>(f0);
-    a.q0 = P<const int>(q0);
-    a.P = Pn; a.K = K; a.iters = iters; a.V = V;
-    a.npa = (int)pa.size();
-    for (size_t i = 0; i < pa.size(); ++i) a.pa_idx[i] = pa[i];
-    a.values = P<const int64_t>(values);
-    a.Pp = Pp;
-    a.pairs = P<const int64_t>(pairs);
-    a.nfree = (int)free_dims.size();
-    for (size_t i = 0; i < free_dims.size(); ++i) a.free_idx[i] = free_dims[i];
-    a.found = P<uint8_t>(found);
-    a.wit_x = P<float>(wit_x);
-    a.wit_xp = P<float>(wit_xp);
-    const int rc = fa_ascent_launch(net.d, a, (hipStream_t)stream);
+    fill_query(a, k, "too many PA/free dims");
+    fill_ascent(a, k, "too many PA/free dims");
+    a.x0 = k.need<const float>("x0");
+    a.f0 = k.need<const float>("f0");
+    a.q0 = k.need<const int>("q0");
+    const int rc = fa_ascent_launch(net.d, a, finish(k));
     if (rc == -1) return false;
     ckl(rc, "ascent");
     return true;
@@ -409,41 +420,27 @@ PYBIND11_MODULE(_C, m) {
 
   // fused residual falsifier; returns false when the network shape is not supported (caller
   // keeps the PyTorch path)
-  m.def("falsify", [](const Net& net, uintptr_t flat, uintptr_t lo, uintptr_t hi, uintptr_t pids, int Pn,
-                      int n_samples, int n_local, uint32_t seed, int V, const std::vector<int>& pa, uintptr_t values,
-                      int Pp, uintptr_t pairs, int walk_k, int walk_steps, int K, int iters,
-                      const std::vector<int>& free_dims, uintptr_t found, uintptr_t wit_x, uintptr_t wit_xp,
-                      uintptr_t how, uintptr_t stream, const std::vector<int>& ra, int tau, uint32_t dseed) {
-    if (pa.size() > FA_MAX_PA || free_dims.size() > 64 || ra.size() > FA_MAX_RA)
-      throw std::invalid_argument("too many PA/RA/free dims");
+  m.def("falsify", [](const Net& net, py::kwargs kw) {
+    Kw k("falsify", kw);
     FalsifyArgs a{};
-    a.flat = P<const float>(flat);
-    a.lo = P<const float>(lo);
-    a.hi = P<const float>(hi);
-    a.pids = P<const int64_t>(pids);
-    a.P = Pn; a.n_samples = n_samples; a.n_local = n_local; a.seed = seed;
-    a.V = V;
-    a.npa = (int)pa.size();
-    for (size_t i = 0; i < pa.size(); ++i) a.pa_idx[i] = pa[i];
-    a.values = P<const int64_t>(values);
-    a.Pp = Pp;
-    a.pairs = P<const int64_t>(pairs);
-    a.walk_k = walk_k; a.walk_steps = walk_steps; a.K = K; a.iters = iters;
-    a.nfree = (int)free_dims.size();
-    for (size_t i = 0; i < free_dims.size(); ++i) a.free_idx[i] = free_dims[i];
-    a.found = P<uint8_t>(found);
-    a.wit_x = P<float>(wit_x);
-    a.wit_xp = P<float>(wit_xp);
-    a.how = P<int8_t>(how);
-    a.nra = tau > 0 ? (int)ra.size() : 0;
-    for (int i = 0; i < a.nra; ++i) a.ra_idx[i] = ra[i];
-    a.tau = tau;
-    a.dseed = dseed;
-    const int rc = fa_falsify_launch(net.d, a, (hipStream_t)stream);
+    fill_query(a, k, "too many PA/RA/free dims");
+    fill_samples(a, k, "too many PA/RA/free dims");
+    fill_ascent(a, k, "too many PA/RA/free dims");
+    if (a.tau <= 0) {                       // not relaxed: no RA offsets
+      a.nra = 0;
+      std::fill_n(a.ra_idx, FA_MAX_RA, 0);
+    }
+    a.n_local = k.i("n_local");
+    a.walk_k = k.i("walk_k");
+    a.walk_steps = k.i("walk_steps");
+    a.how = k.need<int8_t>("how");
+    a.dseed = (uint32_t)k.u64("dseed");
+    const int rc = fa_falsify_launch(net.d, a, finish(k));
     if (rc == 0) return false;
     if (rc < 0) ckl(-rc, "falsify");
     return true;
   });
+
 
   m.def("prune_masks", [](const Net& net, int Pn, uintptr_t counts, uintptr_t ub, int ub_stride, uintptr_t sym_dead,
                           uintptr_t code, uintptr_t cnt, uintptr_t stream) {
@@ -472,40 +469,30 @@ PYBIND11_MODULE(_C, m) {
     return true;
   });
 
-  m.def("certify", [](int Nn, int n0, int V, int Pp, int norient, std::vector<uintptr_t> fx, std::vector<uintptr_t> fxp,
-                      uintptr_t xlo, uintptr_t xhi, uintptr_t xplo, uintptr_t xphi, uintptr_t pairs, uintptr_t values,
-                      const std::vector<int>& pa, const std::vector<int>& ra, double tau, uintptr_t shared,
-                      double unit, double gmarg, uintptr_t gmin, uintptr_t tstar, uintptr_t open, uintptr_t score,
-                      uintptr_t split_dim, uintptr_t cand_x, uintptr_t cand_xp, uintptr_t cand_v, uintptr_t cand_o,
-                      uintptr_t scores, uintptr_t leaf, uintptr_t stream) {
-    if (pa.size() > FA_CMAX_PA || ra.size() > FA_MAX_RA) throw std::invalid_argument("too many PA/RA dims");
-    if (fx.size() != 8 || fxp.size() != 8) throw std::invalid_argument("need 8 form pointers (6 forms + lb/ub)");
+  m.def("certify", [](py::kwargs kw) {
+    Kw k("certify", kw);
+    auto in = [&](const char* key) { return k.need<const float>(key); };
     CertArgs a{};
-    a.Nn = Nn; a.n0 = n0; a.V = V; a.Pp = Pp; a.norient = norient;
-    a.Lc = P<const float>(fx[0]); a.L0 = P<const float>(fx[1]); a.Le = P<const float>(fx[2]);
-    a.Uc = P<const float>(fx[3]); a.U0 = P<const float>(fx[4]); a.Ue = P<const float>(fx[5]);
-    a.olb = P<const float>(fx[6]); a.oub = P<const float>(fx[7]);
-    a.Lcp = P<const float>(fxp[0]); a.L0p = P<const float>(fxp[1]); a.Lep = P<const float>(fxp[2]);
-    a.Ucp = P<const float>(fxp[3]); a.U0p = P<const float>(fxp[4]); a.Uep = P<const float>(fxp[5]);
-    a.olbp = P<const float>(fxp[6]); a.oubp = P<const float>(fxp[7]);
-    a.xlo = P<const float>(xlo); a.xhi = P<const float>(xhi);
-    a.xplo = P<const float>(xplo); a.xphi = P<const float>(xphi);
-    a.pairs = P<const int64_t>(pairs);
-    a.values = P<const int64_t>(values);
-    a.npa = (int)pa.size();
-    for (size_t i = 0; i < pa.size(); ++i) a.pa_idx[i] = pa[i];
-    a.nra = (int)ra.size();
-    for (size_t i = 0; i < ra.size(); ++i) a.ra_idx[i] = ra[i];
-    a.tau = (float)tau;
-    a.shared = P<const uint8_t>(shared);
-    a.unit = (float)unit;
-    a.gmarg = std::nextafter((float)gmarg, INFINITY);
-    a.gmin = P<float>(gmin); a.tstar = P<float>(tstar);
-    a.open = P<uint8_t>(open); a.score = P<float>(score); a.split_dim = P<int64_t>(split_dim);
-    a.cand_x = P<float>(cand_x); a.cand_xp = P<float>(cand_xp);
-    a.cand_v = P<int64_t>(cand_v); a.cand_o = P<int64_t>(cand_o);
-    a.scores = P<float>(scores); a.leaf = P<uint8_t>(leaf);
-    ckl(fa_certify_launch(a, (hipStream_t)stream), "certify");
+    a.Nn = k.i("Nn"); a.n0 = k.i("n0"); a.V = k.i("V"); a.Pp = k.i("Pp"); a.norient = k.i("norient");
+    a.Lc = in("Lc"); a.L0 = in("L0"); a.Le = in("Le"); a.Uc = in("Uc"); a.U0 = in("U0"); a.Ue = in("Ue");
+    a.olb = in("olb"); a.oub = in("oub");
+    a.Lcp = in("Lcp"); a.L0p = in("L0p"); a.Lep = in("Lep"); a.Ucp = in("Ucp"); a.U0p = in("U0p"); a.Uep = in("Uep");
+    a.olbp = in("olbp"); a.oubp = in("oubp");
+    a.xlo = in("xlo"); a.xhi = in("xhi"); a.xplo = in("xplo"); a.xphi = in("xphi");
+    a.pairs = k.ptr<const int64_t>("pairs");
+    a.values = k.ptr<const int64_t>("values");
+    a.npa = dims(k, "pa", a.pa_idx, FA_CMAX_PA, "too many PA/RA dims");
+    a.nra = dims(k, "ra", a.ra_idx, FA_MAX_RA, "too many PA/RA dims");
+    a.tau = k.f("tau");
+    a.shared = k.need<const uint8_t>("shared");
+    a.unit = k.f("unit");
+    a.gmarg = std::nextafter(k.f("gmarg"), INFINITY);
+    a.gmin = k.ptr<float>("gmin"); a.tstar = k.ptr<float>("tstar");     // [Nn, Q]: empty without pairs
+    a.open = k.need<uint8_t>("open"); a.score = k.need<float>("score"); a.split_dim = k.need<int64_t>("split_dim");
+    a.cand_x = k.need<float>("cand_x"); a.cand_xp = k.need<float>("cand_xp");
+    a.cand_v = k.need<int64_t>("cand_v"); a.cand_o = k.need<int64_t>("cand_o");
+    a.scores = k.ptr<float>("scores"); a.leaf = k.ptr<uint8_t>("leaf");
+    ckl(fa_certify_launch(a, finish(k)), "certify");
   });
 
   m.def("decode", [](std::vector<int> radix, std::vector<long long> div, std::vector<int> chunk_off,
@@ -547,129 +534,52 @@ PYBIND11_MODULE(_C, m) {
   m.def("trace_marker", [](int tag, uintptr_t sink, uintptr_t stream) {
     ckl(fa_trace_marker_launch(tag, P<int>(sink), (hipStream_t)stream), "trace_marker");
   });
-  // the arguments of one beta level (beta_level and the batched entry points share them)
-  auto beta_args = [](const Net& net, uintptr_t flat, uintptr_t wt, int R, const std::vector<int>& pa, uintptr_t lo,
-                      uintptr_t hi, uintptr_t va, uintptr_t vb, uintptr_t LBA, uintptr_t UBA, uintptr_t LBB,
-                      uintptr_t UBB, uintptr_t phA, uintptr_t phB, uintptr_t par, uintptr_t t, uintptr_t scratch,
-                      int iters, float lr_a, float lr_b, float lr_t, float decay, int lookahead, int beta_pos,
-                      int stall, uintptr_t bound, uintptr_t split, uintptr_t xstar, uintptr_t binit,
-                      unsigned long long ramask, uintptr_t plo, uintptr_t phi, uintptr_t xpstar, uintptr_t gtie,
-                      float tau, uintptr_t osg) {
-    if (pa.size() > FA_MAX_PA) throw std::invalid_argument("beta_level: too many PA dims");
-    for (size_t q = 0; q < pa.size(); ++q)
-      if (pa[q] < 0 || pa[q] >= net.d.dims[0] || (q && pa[q] <= pa[q - 1]))
-        throw std::invalid_argument("beta_level: PA dims must be increasing input indices");
-    BetaArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.flat = P<const float>(flat);
-    a.wt = P<const float>(wt);
-    a.R = R;
-    a.npa = (int)pa.size();
-    for (size_t q = 0; q < pa.size(); ++q) a.pa_idx[q] = pa[q];
-    a.lo = P<const float>(lo);
-    a.hi = P<const float>(hi);
-    a.va = P<const float>(va);
-    a.vb = P<const float>(vb);
-    a.LBA = P<const float>(LBA);
-    a.UBA = P<const float>(UBA);
-    a.LBB = P<const float>(LBB);
-    a.UBB = P<const float>(UBB);
-    a.phA = P<const int8_t>(phA);
-    a.phB = P<const int8_t>(phB);
-    a.par = P<float>(par);
-    a.t = P<float>(t);
-    a.scratch = P<float>(scratch);
-    a.iters = iters;
-    a.lr_a = lr_a;
-    a.lr_b = lr_b;
-    a.lr_t = lr_t;
-    a.decay = decay;
-    a.lookahead = lookahead;
-    a.beta_pos = beta_pos;
-    a.stall = stall & 1;        // bit 1: primal-gap branching (ops/hip.py:beta_level)
-    a.pgap = (stall >> 1) & 3;
-    a.feas = (stall >> 3) & 1;  // bit 3: the infeasibility pass (scratch [R, 16, NH])
-    a.bound = P<double>(bound);
-    a.split = P<int>(split);
-    a.xstar = P<float>(xstar);
-    a.binit = P<float>(binit);
-    a.ramask = ramask;
-    a.plo = P<const float>(plo);
-    a.phi = P<const float>(phi);
-    a.xpstar = P<float>(xpstar);
-    a.gtie = P<float>(gtie);
-    a.tau = tau;
-    a.osg = P<const int8_t>(osg);
-    if ((net.d.dims[0] < 64 && (ramask >> net.d.dims[0])) || (ramask && (!plo || !phi)))
-      throw std::invalid_argument("beta_level: RA mask beyond the inputs or no x' box");
-    return a;
-  };
-  m.def("beta_level", [beta_args](const Net& net, uintptr_t flat, uintptr_t wt, int R, std::vector<int> pa,
-                                  uintptr_t lo, uintptr_t hi, uintptr_t va, uintptr_t vb, uintptr_t LBA,
-                                  uintptr_t UBA, uintptr_t LBB, uintptr_t UBB, uintptr_t phA, uintptr_t phB,
-                                  uintptr_t par, uintptr_t t, uintptr_t scratch, int iters, float lr_a, float lr_b,
-                                  float lr_t, float decay, int lookahead, int beta_pos, int stall, uintptr_t bound,
-                                  uintptr_t split, uintptr_t xstar, uintptr_t binit, unsigned long long ramask,
-                                  uintptr_t plo, uintptr_t phi, uintptr_t xpstar, uintptr_t gtie, float tau,
-                                  uintptr_t osg, uintptr_t stream) {
-    const BetaArgs a = beta_args(net, flat, wt, R, pa, lo, hi, va, vb, LBA, UBA, LBB, UBB, phA, phB, par, t, scratch,
-                                 iters, lr_a, lr_b, lr_t, decay, lookahead, beta_pos, stall, bound, split, xstar,
-                                 binit, ramask, plo, phi, xpstar, gtie, tau, osg);
-    return fa_beta_launch(net.d, a, reinterpret_cast<hipStream_t>(stream));
+  // The beta entries return the launch code (0 done).
+  m.def("beta_level", [](const Net& net, py::kwargs kw) {
+    Kw k("beta_level", kw);
+    const BetaArgs a = beta_args(net, k);
+    return fa_beta_launch(net.d, a, finish(k));
   });
   // two-phase level (csrc/beta_opt16.hip): the batched MFMA optimiser, then fa_beta_kernel at iters = 0
   // seeded with its primal sums pgsum [R, 4, NH] / pgn [R]; scratch must hold
   // max(R * 12 * NH, beta_opt16_scratch(R)) floats
-  m.def("beta_level16", [beta_args](const Net& net, uintptr_t flat, uintptr_t wt, int R, std::vector<int> pa,
-                                    uintptr_t lo, uintptr_t hi, uintptr_t va, uintptr_t vb, uintptr_t LBA,
-                                    uintptr_t UBA, uintptr_t LBB, uintptr_t UBB, uintptr_t phA, uintptr_t phB,
-                                    uintptr_t par, uintptr_t t, uintptr_t scratch, int iters, float lr_a, float lr_b,
-                                    float lr_t, float decay, int lookahead, int beta_pos, int stall, uintptr_t bound,
-                                    uintptr_t split, uintptr_t xstar, uintptr_t binit, unsigned long long ramask,
-                                    uintptr_t plo, uintptr_t phi, uintptr_t xpstar, uintptr_t gtie, float tau,
-                                    uintptr_t osg, uintptr_t pgsum, uintptr_t pgn, uintptr_t stream) {
-    BetaArgs a = beta_args(net, flat, wt, R, pa, lo, hi, va, vb, LBA, UBA, LBB, UBB, phA, phB, par, t, scratch, iters,
-                           lr_a, lr_b, lr_t, decay, lookahead, beta_pos, stall, bound, split, xstar, binit, ramask,
-                           plo, phi, xpstar, gtie, tau, osg);
-    a.pgsum = P<const float>(pgsum);
-    a.pgn = P<const float>(pgn);
-    return fa_beta_level16_launch(net.d, a, reinterpret_cast<hipStream_t>(stream));
+  m.def("beta_level16", [](const Net& net, py::kwargs kw) {
+    Kw k("beta_level16", kw);
+    const BetaArgs a = beta_args(net, k);
+    return fa_beta_level16_launch(net.d, a, finish(k));
   });
-  // phase 1 alone: par / t / gtie optimised in place (best iterate), pgsum / pgn written
-  m.def("beta_opt16", [beta_args](const Net& net, uintptr_t flat, int R, std::vector<int> pa, uintptr_t lo,
-                                  uintptr_t hi, uintptr_t va, uintptr_t vb, uintptr_t LBA, uintptr_t UBA,
-                                  uintptr_t LBB, uintptr_t UBB, uintptr_t phA, uintptr_t phB, uintptr_t par,
-                                  uintptr_t t, uintptr_t scratch, int iters, float lr_a, float lr_b, float lr_t,
-                                  float decay, int beta_pos, int pgap, unsigned long long ramask, uintptr_t plo,
-                                  uintptr_t phi, uintptr_t gtie, float tau, uintptr_t osg, uintptr_t pgsum,
-                                  uintptr_t pgn, uintptr_t stream) {
-    const BetaArgs a = beta_args(net, flat, 0, R, pa, lo, hi, va, vb, LBA, UBA, LBB, UBB, phA, phB, par, t, scratch,
-                                 iters, lr_a, lr_b, lr_t, decay, 0, beta_pos, (pgap & 3) << 1, 0, 0, 0, 0, ramask,
-                                 plo, phi, 0, gtie, tau, osg);
-    return fa_beta_opt16_launch(net.d, a, P<float>(pgsum), P<float>(pgn), reinterpret_cast<hipStream_t>(stream));
+  // phase 1 alone: par / t / gtie optimised in place (best iterate), pgsum / pgn written; no wt
+  m.def("beta_opt16", [](const Net& net, py::kwargs kw) {
+    Kw k("beta_opt16", kw);
+    BetaArgs a = beta_args(net, k);
+    float* pgsum = const_cast<float*>(a.pgsum);
+    float* pgn = const_cast<float*>(a.pgn);
+    a.wt = a.pgsum = a.pgn = nullptr;
+    return fa_beta_opt16_launch(net.d, a, pgsum, pgn, finish(k));
   });
   // the infeasibility pass alone on rows whose main-pass outputs (par, t, gtie, bound) are given.  mode 0:
   // the per-node pass (fa_beta_kernel, feas = 1, `iters` steps; scratch [R, 16, NH]); 1: the two-phase
   // pass (proposals to fpar [R, 4, NH] / fgt [R, 2, n0] by the batched optimiser's feas mode, then the
   // per-node kernel at iters = 0 on them; scratch max(R * 16 * NH, beta_opt16_scratch(R))); 2: the
   // proposal phase alone; 3: the rigorous phase alone on the fpar / fgt given.  fval [R] (optional):
-  // the rigorous value of the rows that ran.  bound: +inf written on the rows the pass closes
-  m.def("beta_feas", [beta_args](const Net& net, uintptr_t flat, uintptr_t wt, int R, std::vector<int> pa, uintptr_t lo,
-                                 uintptr_t hi, uintptr_t va, uintptr_t vb, uintptr_t LBA, uintptr_t UBA, uintptr_t LBB,
-                                 uintptr_t UBB, uintptr_t phA, uintptr_t phB, uintptr_t par, uintptr_t t,
-                                 uintptr_t scratch, int iters, float lr_a, float lr_b, float lr_t, float decay,
-                                 uintptr_t bound, unsigned long long ramask, uintptr_t plo, uintptr_t phi,
-                                 uintptr_t gtie, float tau, uintptr_t osg, uintptr_t fpar, uintptr_t fgt,
-                                 uintptr_t fval, int mode, uintptr_t stream) {
-    BetaArgs a = beta_args(net, flat, wt, R, pa, lo, hi, va, vb, LBA, UBA, LBB, UBB, phA, phB, par, t, scratch, iters,
-                           lr_a, lr_b, lr_t, decay, 0, 1, 8, bound, 0, 0, 0, ramask, plo, phi, 0, gtie, tau, osg);
+  // the rigorous value of the rows that ran.  bound: +inf written on the rows the pass closes.  Takes a
+  // level's keywords: its branching keys (lookahead, beta_pos, flags, split, xstar, binit, xpstar) are
+  // read and overridden
+  m.def("beta_feas", [](const Net& net, py::kwargs kw) {
+    Kw k("beta_feas", kw);
+    BetaArgs a = beta_args(net, k);
+    const int mode = k.i("mode");
+    const hipStream_t st = finish(k);
     if (mode < 0 || mode > 3) throw std::invalid_argument("beta_feas: mode must be 0..3");
-    if (mode != 0 && !fpar) throw std::invalid_argument("beta_feas: fpar required");
-    a.fval = P<double>(fval);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (mode == 0) return fa_beta_launch(net.d, a, st);
-    a.fpar = P<float>(fpar);
-    a.fgt = P<float>(fgt);
+    if (mode != 0 && !a.fpar) throw std::invalid_argument("beta_feas: fpar required");
+    a.lookahead = a.stall = a.pgap = 0;
+    a.beta_pos = a.feas = 1;
+    a.split = nullptr;
+    a.xstar = a.binit = a.xpstar = nullptr;
+    if (mode == 0) {
+      a.fpar = a.fgt = nullptr;
+      return fa_beta_launch(net.d, a, st);
+    }
     if (mode == 1) return fa_beta_feas16_launch(net.d, a, st);
     if (mode == 2) return fa_beta_opt16_feas_launch(net.d, a, st);
     a.iters = 0;

@@ -62,6 +62,35 @@ def _ptr(t: Optional[torch.Tensor]) -> int:
     return 0 if t is None else t.data_ptr()
 
 
+def _ptrs(**tensors) -> dict:
+    """Keyword pointers for the struct-filling bindings (key = the ``args.h`` field name); a ``None``
+    tensor's key is left out, which the binding reads as a null pointer."""
+    return {k: t.data_ptr() for k, t in tensors.items() if t is not None}
+
+
+def _bound_kw(be, lo, hi, dead=None, res=None, layer_lb=None, layer_ub=None):
+    """The block the bound-family bindings share: ``(keywords, tensors)`` -- row boxes, forced-dead
+    mask, ``res``'s logit bounds and forms, layer bounds, R and the stream.  The checked contiguous
+    ``tensors`` (same keys) must stay alive until the launch is enqueued."""
+    R, n0 = lo.shape
+    t = dict(flat=be.flat, lo=_c(lo, torch.float32, (R, n0), "lo"), hi=_c(hi, torch.float32, (R, n0), "hi"),
+             dead_in=None if dead is None else _c(dead, torch.uint8, (R, be.n_hidden), "dead"),
+             layer_lb=layer_lb, layer_ub=layer_ub)
+    if res is not None:
+        t.update(out_lb=res.out_lb, out_ub=res.out_ub, Lc=res.Lc, L0=res.L0, Le=res.Le, Uc=res.Uc, U0=res.U0,
+                 Ue=res.Ue)
+    return dict(_ptrs(**t), R=R, stream=_stream(lo.device)), t
+
+
+def _layer_views(be, lay_lb, lay_ub):
+    """Per-layer column views of [R, n_neurons] layer bounds."""
+    offs = [0]
+    for w in be.mlp.widths:
+        offs.append(offs[-1] + w)
+    n = len(be.mlp.widths)
+    return [lay_lb[:, offs[i]:offs[i + 1]] for i in range(n)], [lay_ub[:, offs[i]:offs[i + 1]] for i in range(n)]
+
+
 # ------------------------------------------------------------------------------------------------
 def decode(grid, ids: torch.Tensor):
     """K1: grid-linear partition ids (int64, on the device) -> boxes ``lo, hi`` float32 [P, n0]
@@ -171,8 +200,8 @@ def point_bounds(be, x: torch.Tensor, dead: Optional[torch.Tensor] = None):
     if dead is not None:
         d = _c(dead, torch.uint8, (R, be.n_hidden), "dead")
     if R:
-        ext().point_bounds(_net(be), be.flat.data_ptr(), x2.data_ptr(), _ptr(d), R, lb.data_ptr(), ub.data_ptr(),
-                           _stream(x.device))
+        ext().point_bounds(_net(be), **_ptrs(flat=be.flat, x=x2, dead_in=d, out_lb=lb, out_ub=ub), R=R,
+                           stream=_stream(x.device))
     return lb, ub
 
 
@@ -186,14 +215,9 @@ def bounds(be, lo: torch.Tensor, hi: torch.Tensor, mode: str = "symbolic", dead:
     if n0 != be.n0:
         raise ValueError(f"box width {n0} != network input {be.n0}")
     dev = lo.device
-    lo = _c(lo, torch.float32, (R, n0), "lo")
-    hi = _c(hi, torch.float32, (R, n0), "hi")
     sym = 1 if mode == "symbolic" else 0
     f32 = dict(dtype=torch.float32, device=dev)
-    out_lb = torch.empty(R, **f32)
-    out_ub = torch.empty(R, **f32)
-    res = ref.BoundResult(out_lb=out_lb, out_ub=out_ub)
-    forms = [None] * 6
+    res = ref.BoundResult(out_lb=torch.empty(R, **f32), out_ub=torch.empty(R, **f32))
     if sym:
         res.Lc = torch.empty(R, n0, **f32)
         res.L0 = torch.empty(R, **f32)
@@ -201,34 +225,24 @@ def bounds(be, lo: torch.Tensor, hi: torch.Tensor, mode: str = "symbolic", dead:
         res.Uc = torch.empty(R, n0, **f32)
         res.U0 = torch.empty(R, **f32)
         res.Ue = torch.empty(R, **f32)
-        forms = [res.Lc, res.L0, res.Le, res.Uc, res.U0, res.Ue]
     N = be.mlp.n_neurons
     lay_lb = lay_ub = None
     if keep_layers:
         lay_lb = torch.empty(R, N, **f32)
         lay_ub = torch.empty(R, N, **f32)
     dead_out = torch.empty(R, be.n_hidden, dtype=torch.uint8, device=dev) if be.n_hidden else None
-    d = None
-    if dead is not None:
-        d = _c(dead, torch.uint8, (R, be.n_hidden), "dead")
     ph = infeas = None
     if phase is not None:
         ph = _c(phase, torch.int8, (R, be.n_hidden), "phase")
         infeas = torch.zeros(R, dtype=torch.uint8, device=dev)
+    kw, _keep = _bound_kw(be, lo, hi, dead, res, lay_lb, lay_ub)
     if R:
-        ext().bounds(_net(be), be.flat.data_ptr(), lo.data_ptr(), hi.data_ptr(), _ptr(d), R, sym,
-                     out_lb.data_ptr(), out_ub.data_ptr(), *[_ptr(t) for t in forms],
-                     _ptr(lay_lb), _ptr(lay_ub), _ptr(dead_out), G, _stream(dev), _fold_mask(fold, n0),
-                     _ptr(ph), _ptr(infeas))
+        ext().bounds(_net(be), **kw, **_ptrs(dead_out=dead_out, phase_in=ph, infeas=infeas), symbolic=sym, G=G,
+                     fold=_fold_mask(fold, n0))
     if infeas is not None:
         res.infeasible = infeas.bool()
     if keep_layers:
-        widths = be.mlp.widths
-        offs = [0]
-        for w in widths:
-            offs.append(offs[-1] + w)
-        res.layer_lb = [lay_lb[:, offs[i]:offs[i + 1]] for i in range(len(widths))]
-        res.layer_ub = [lay_ub[:, offs[i]:offs[i + 1]] for i in range(len(widths))]
+        res.layer_lb, res.layer_ub = _layer_views(be, lay_lb, lay_ub)
         res.lay_lb_full, res.lay_ub_full = lay_lb, lay_ub
     if dead_out is not None:
         res.dead_u8 = dead_out
@@ -244,22 +258,15 @@ def crown(be, lo: torch.Tensor, hi: torch.Tensor, res: ref.BoundResult, dead: Op
     N = be.mlp.n_neurons
     if res.Lc is None or res.layer_lb is None:
         raise ValueError("crown needs symbolic bounds with keep_layers=True")
-    lo = _c(lo, torch.float32, (R, n0), "lo")
-    hi = _c(hi, torch.float32, (R, n0), "hi")
     lay_lb = torch.cat(res.layer_lb, dim=1).contiguous() if isinstance(res.layer_lb, list) else res.layer_lb
     lay_ub = torch.cat(res.layer_ub, dim=1).contiguous() if isinstance(res.layer_ub, list) else res.layer_ub
     if lay_lb.shape[1] != N:          # keep_layers splits off the output neuron: append a pad column
         pad = torch.zeros(R, N - lay_lb.shape[1], dtype=torch.float32, device=lo.device)
         lay_lb = torch.cat([lay_lb, pad], dim=1).contiguous()
         lay_ub = torch.cat([lay_ub, pad], dim=1).contiguous()
-    d = None
-    if dead is not None:
-        d = _c(dead, torch.uint8, (R, be.n_hidden), "dead")
+    kw, _keep = _bound_kw(be, lo, hi, dead, res, lay_lb, lay_ub)
     if R:
-        ext().crown(_net(be), be.flat.data_ptr(), lo.data_ptr(), hi.data_ptr(), _ptr(d), R,
-                    res.out_lb.data_ptr(), res.out_ub.data_ptr(), res.Lc.data_ptr(), res.L0.data_ptr(),
-                    res.Le.data_ptr(), res.Uc.data_ptr(), res.U0.data_ptr(), res.Ue.data_ptr(),
-                    lay_lb.data_ptr(), lay_ub.data_ptr(), _stream(lo.device))
+        ext().crown(_net(be), **kw)
     return res
 
 
@@ -275,17 +282,11 @@ def refine(be, lo: torch.Tensor, hi: torch.Tensor, res: ref.BoundResult, dead: O
     R, n0 = lo.shape
     if res.lay_lb_full is None:
         raise ValueError("refine needs symbolic bounds with keep_layers=True (HIP layout)")
-    lo = _c(lo, torch.float32, (R, n0), "lo")
-    hi = _c(hi, torch.float32, (R, n0), "hi")
-    d = None
-    if dead is not None:
-        d = _c(dead, torch.uint8, (R, be.n_hidden), "dead")
+    kw, _keep = _bound_kw(be, lo, hi, dead, None, res.lay_lb_full, res.lay_ub_full)
     ph = _c(phase, torch.int8, (R, be.n_hidden), "phase") if phase is not None else None
     infeas = torch.zeros(R, dtype=torch.uint8, device=lo.device) if phase is not None else None
     if R:
-        ext().refine(_net(be), be.flat.data_ptr(), lo.data_ptr(), hi.data_ptr(), _ptr(d), R,
-                     res.lay_lb_full.data_ptr(), res.lay_ub_full.data_ptr(), _stream(lo.device), _ptr(ph),
-                     _ptr(infeas))
+        ext().refine(_net(be), **kw, **_ptrs(phase_in=ph, infeas=infeas))
     if infeas is not None:
         res.infeasible = infeas.bool() if res.infeasible is None else (res.infeasible | infeas.bool())
     Nh = be.n_hidden
@@ -302,36 +303,22 @@ def backward_bounds(be, lo: torch.Tensor, hi: torch.Tensor, dead: Optional[torch
     """Every neuron's bounds and the logit's forms by back-substitution alone (csrc/refine.hip mode
     FULL, ref.backward_bounds).  ``None`` when the network does not fit the kernel."""
     R, n0 = lo.shape
-    dev = lo.device
-    lo = _c(lo, torch.float32, (R, n0), "lo")
-    hi = _c(hi, torch.float32, (R, n0), "hi")
-    f32 = dict(dtype=torch.float32, device=dev)
+    f32 = dict(dtype=torch.float32, device=lo.device)
     res = ref.BoundResult(out_lb=torch.empty(R, **f32), out_ub=torch.empty(R, **f32),
                           Lc=torch.empty(R, n0, **f32), L0=torch.empty(R, **f32), Le=torch.empty(R, **f32),
                           Uc=torch.empty(R, n0, **f32), U0=torch.empty(R, **f32), Ue=torch.empty(R, **f32))
     N = be.mlp.n_neurons
     lay_lb = torch.empty(R, N, **f32) if keep_layers else None
     lay_ub = torch.empty(R, N, **f32) if keep_layers else None
-    d = None
-    if dead is not None:
-        d = _c(dead, torch.uint8, (R, be.n_hidden), "dead")
-    if R:
-        rc = ext().backward_bounds(_net(be), be.flat.data_ptr(), lo.data_ptr(), hi.data_ptr(), _ptr(d), R,
-                                   res.out_lb.data_ptr(), res.out_ub.data_ptr(), res.Lc.data_ptr(), res.L0.data_ptr(),
-                                   res.Le.data_ptr(), res.Uc.data_ptr(), res.U0.data_ptr(), res.Ue.data_ptr(),
-                                   _ptr(lay_lb), _ptr(lay_ub), _stream(dev))
-        if rc == -1:
-            return None
+    kw, keep = _bound_kw(be, lo, hi, dead, res, lay_lb, lay_ub)
+    if R and ext().backward_bounds(_net(be), **kw) == -1:
+        return None
     if keep_layers:
-        widths = be.mlp.widths
-        offs = [0]
-        for w in widths:
-            offs.append(offs[-1] + w)
-        res.layer_lb = [lay_lb[:, offs[i]:offs[i + 1]] for i in range(len(widths))]
-        res.layer_ub = [lay_ub[:, offs[i]:offs[i + 1]] for i in range(len(widths))]
+        res.layer_lb, res.layer_ub = _layer_views(be, lay_lb, lay_ub)
         res.lay_lb_full, res.lay_ub_full = lay_lb, lay_ub
         Nh = be.n_hidden
         res.dead = lay_ub[:, :Nh] <= 0
+        d = keep["dead_in"]
         if d is not None:
             res.dead = res.dead | d.bool()
         res.active = (lay_lb[:, :Nh] >= 0) & ~res.dead
@@ -346,21 +333,16 @@ def crown_phase(be, lo: torch.Tensor, hi: torch.Tensor, res: ref.BoundResult, ph
     (ref.PhaseCrown, None) -- the kernel writes the better input forms into ``res`` directly."""
     R, n0 = lo.shape
     dev = lo.device
-    lo = _c(lo, torch.float32, (R, n0), "lo")
-    hi = _c(hi, torch.float32, (R, n0), "hi")
     if res.lay_lb_full is None:
         raise ValueError("crown_phase needs bounds(..., keep_layers=True) from the HIP path")
+    kw, _keep = _bound_kw(be, lo, hi, None, res, res.lay_lb_full, res.lay_ub_full)
     ph = _c(phase, torch.int8, (R, be.n_hidden), "phase") if phase is not None else None
     split = torch.full((R, 2), -1, dtype=torch.int32, device=dev)
     score = torch.zeros(R, 2, dtype=torch.float32, device=dev)
     low = torch.zeros(R, 2, dtype=torch.float32, device=dev)
     infeas = res.infeasible.to(torch.uint8).contiguous() if res.infeasible is not None else None
     if R:
-        ext().crown_phase(_net(be), be.flat.data_ptr(), lo.data_ptr(), hi.data_ptr(), R, _ptr(ph),
-                          res.lay_lb_full.data_ptr(), res.lay_ub_full.data_ptr(), _ptr(infeas),
-                          res.out_lb.data_ptr(), res.out_ub.data_ptr(), res.Lc.data_ptr(), res.L0.data_ptr(),
-                          res.Le.data_ptr(), res.Uc.data_ptr(), res.U0.data_ptr(), res.Ue.data_ptr(),
-                          split.data_ptr(), score.data_ptr(), low.data_ptr(), _stream(dev))
+        ext().crown_phase(_net(be), **kw, **_ptrs(phase=ph, infeas=infeas, split=split, score=score, low=low))
     return ref.PhaseCrown(low=low, split=split.long(), score=score), None
 
 
@@ -392,19 +374,20 @@ def pair_certify(be, res_x, res_xp, xlo, xhi, xplo, xphi, pairs, values, pa, sha
     cxp = torch.empty(Nn, n0, **f32)
     cv = torch.empty(Nn, dtype=torch.int64, device=dev)
     co = torch.empty(Nn, dtype=torch.int64, device=dev)
-    fx = [res_x.Lc, res_x.L0, res_x.Le, res_x.Uc, res_x.U0, res_x.Ue, res_x.out_lb, res_x.out_ub]
-    fxp = [res_xp.Lc, res_xp.L0, res_xp.Le, res_xp.Uc, res_xp.U0, res_xp.Ue, res_xp.out_lb, res_xp.out_ub]
-    fx = [_c(t, torch.float32) for t in fx]
-    fxp = [_c(t, torch.float32) for t in fxp]
+    # the forms and logit bounds of the x rows, and (key + "p") of the x' rows
+    forms = {}
+    for r, p in ((res_x, ""), (res_xp, "p")):
+        for key, t in (("Lc", r.Lc), ("L0", r.L0), ("Le", r.Le), ("Uc", r.Uc), ("U0", r.U0), ("Ue", r.Ue),
+                       ("olb", r.out_lb), ("oub", r.out_ub)):
+            forms[key + p] = _c(t, torch.float32)
     scores = torch.empty(Nn, 2 * n0, **f32)
     leaf = torch.empty(Nn, dtype=torch.uint8, device=dev)
     if Nn:
-        ext().certify(Nn, n0, V, Pp, norient, [t.data_ptr() for t in fx], [t.data_ptr() for t in fxp],
-                      xlo.data_ptr(), xhi.data_ptr(), xplo.data_ptr(), xphi.data_ptr(), pairs_c.data_ptr(),
-                      values_c.data_ptr(), [int(i) for i in pa.tolist()], [], 0.0, sh.data_ptr(), be.unit,
-                      ref.gamma(2 * n0 + 4, be.unit), gmin.data_ptr(), tstar.data_ptr(), open_.data_ptr(),
-                      score.data_ptr(), split.data_ptr(), cx.data_ptr(), cxp.data_ptr(), cv.data_ptr(),
-                      co.data_ptr(), scores.data_ptr(), leaf.data_ptr(), _stream(dev))
+        ext().certify(Nn=Nn, n0=n0, V=V, Pp=Pp, norient=norient, pa=[int(i) for i in pa.tolist()], ra=[], tau=0.0,
+                      unit=be.unit, gmarg=ref.gamma(2 * n0 + 4, be.unit), stream=_stream(dev),
+                      **_ptrs(xlo=xlo, xhi=xhi, xplo=xplo, xphi=xphi, pairs=pairs_c, values=values_c, shared=sh,
+                              gmin=gmin, tstar=tstar, open=open_, score=score, split_dim=split, cand_x=cx,
+                              cand_xp=cxp, cand_v=cv, cand_o=co, scores=scores, leaf=leaf, **forms))
     return ref.PairDecision(open_=open_.bool(), score=score, split_dim=split, cand_x=cx, cand_xp=cxp,
                             cand_v=cv, cand_orient=co)
 
@@ -455,18 +438,29 @@ def _sim_regcount() -> bool:
     return os.environ.get("FAIRIFY_SIM_REGCOUNT", "1").strip() != "0"
 
 
+def _query_kw(be, q, lo, hi, pids, values, pairs):
+    """The query block the sampling-family bindings share: ``(keywords, tensors)`` -- boxes, PA table
+    and pairs, P / V / Pp, the stream and, with ``pids`` (the kernels that draw their samples), the RA
+    dims and tau of a relaxed query.  The checked contiguous ``tensors`` (same keys) must stay alive
+    until the launch is enqueued."""
+    P, n0 = lo.shape
+    Pp = pairs.shape[0]
+    t = dict(flat=be.flat, lo=_c(lo, torch.float32, (P, n0), "lo"), hi=_c(hi, torch.float32, (P, n0), "hi"),
+             values=_c(values, torch.int64, None, "values"), pairs=_c(pairs, torch.int64, (Pp, 2), "pairs"))
+    kw = dict(P=P, V=int(values.shape[0]), pa=list(q.pa_idx), Pp=int(Pp), stream=_stream(lo.device))
+    if pids is not None:
+        t["pids"] = _c(pids, torch.int64, (P,), "pids")
+        kw.update(ra=list(q.ra_idx) if q.relaxed else [], tau=int(q.tau) if q.relaxed else 0)
+    kw.update(_ptrs(**t))
+    return kw, t
+
+
 def simulate(be, q, lo, hi, pids, n_samples, seed, values, pairs, bisect_pairs, bisect_steps, return_z0=False):
     from ..engine.sim import SimResult, boundary_walk
 
     P, n0 = lo.shape
     dev = lo.device
-    lo_c = _c(lo, torch.float32, (P, n0), "lo")
-    hi_c = _c(hi, torch.float32, (P, n0), "hi")
-    pids_c = _c(pids, torch.int64, (P,), "pids")
-    V = values.shape[0]
-    Pp = pairs.shape[0]
-    values_c = _c(values, torch.int64, None, "values")
-    pairs_c = _c(pairs, torch.int64, (Pp, 2), "pairs")
+    kw, t = _query_kw(be, q, lo, hi, pids, values, pairs)
     split = _sim_split(P, n_samples)
     counts = (torch.zeros if split > 1 else torch.empty)(P, be.mlp.n_neurons, dtype=torch.int32, device=dev)
     keys = torch.full((P,), 0x7FFFFFFF, dtype=torch.int32, device=dev) if split > 1 else None
@@ -476,16 +470,15 @@ def simulate(be, q, lo, hi, pids, n_samples, seed, values, pairs, bisect_pairs, 
     walk = bool(bisect_pairs and bisect_steps)
     z0 = torch.empty(P, n_samples, dtype=torch.float32, device=dev) if (walk or return_z0) else None
     if P and n_samples:
-        ext().sim(_net(be), be.flat.data_ptr(), lo_c.data_ptr(), hi_c.data_ptr(), pids_c.data_ptr(), P, n_samples,
-                  int(seed) & 0xFFFFFFFF, V, list(q.pa_idx), values_c.data_ptr(), Pp, pairs_c.data_ptr(),
-                  list(q.ra_idx) if q.relaxed else [], int(q.tau), counts.data_ptr(), found.data_ptr(),
-                  wx.data_ptr(), wxp.data_ptr(), _ptr(z0), _ptr(keys), split, int(_sim_regcount()), _stream(dev))
+        kw["tau"] = int(q.tau)          # as given, also where the query is not relaxed (no RA dims then)
+        ext().sim(_net(be), **kw, **_ptrs(counts=counts, found=found, wit_x=wx, wit_xp=wxp, z0=z0, keys=keys),
+                  n_samples=n_samples, seed=int(seed) & 0xFFFFFFFF, split=split, regcount=int(_sim_regcount()))
     res = SimResult(counts=counts, found=found.bool(), wit_x=wx, wit_xp=wxp)
     if return_z0:
         res.z0 = z0
     if walk:
-        boundary_walk(be, q, lo_c, hi_c, pids_c, n_samples, seed, values_c, pairs_c, res, z0, bisect_pairs,
-                      bisect_steps)
+        boundary_walk(be, q, t["lo"], t["hi"], t["pids"], n_samples, seed, t["values"], t["pairs"], res, z0,
+                      bisect_pairs, bisect_steps)
     return res
 
 
@@ -517,16 +510,13 @@ def rate_counts(be, q, lo, hi, pids, n_samples, seed, values, pairs, split: Opti
     dev = lo.device
     if n0 != be.n0:
         raise ValueError(f"lo: expected [P, {be.n0}], got {tuple(lo.shape)}")
-    lo_c = _c(lo, torch.float32, (P, n0), "lo")
-    hi_c = _c(hi, torch.float32, (P, n0), "hi")
-    pids_c = _c(pids, torch.int64, (P,), "pids")
     npa = len(q.pa_idx)
     if values.dim() != 2 or values.shape[1] != npa:
         raise ValueError(f"values: expected [V, {npa}], got {tuple(values.shape)}")
     V = int(values.shape[0])
     Pp = int(pairs.shape[0])
-    values_c = _c(values, torch.int64, (V, npa), "values")
-    pairs_c = _c(pairs, torch.int64, (Pp, 2), "pairs")
+    kw, t = _query_kw(be, q, lo, hi, pids, values, pairs)
+    pairs_c = t["pairs"]
     if not 1 <= V <= 32:
         raise ValueError(f"rate: {V} PA assignments, the kernel covers 1..32")
     if Pp and (int(pairs_c.min()) < 0 or int(pairs_c.max()) >= V):
@@ -546,10 +536,8 @@ def rate_counts(be, q, lo, hi, pids, n_samples, seed, values, pairs, split: Opti
     amb = torch.zeros(P, dtype=torch.int32, device=dev)
     idx = torch.full((P, AMB_SLOTS), _RATE_EMPTY, dtype=torch.int32, device=dev)
     if P and n_samples:
-        ext().rate(_net(be), be.flat.data_ptr(), lo_c.data_ptr(), hi_c.data_ptr(), pids_c.data_ptr(), P, n_samples,
-                   int(seed) & 0xFFFFFFFF, V, list(q.pa_idx), values_c.data_ptr(), Pp, pairs_c.data_ptr(),
-                   list(q.ra_idx) if q.relaxed else [], int(q.tau) if q.relaxed else 0, E, flips.data_ptr(),
-                   amb.data_ptr(), idx.data_ptr(), int(split), _stream(dev))
+        ext().rate(_net(be), **kw, **_ptrs(flips=flips, amb=amb, amb_idx=idx), n_samples=n_samples,
+                   seed=int(seed) & 0xFFFFFFFF, E=E, split=int(split))
         # slots are taken in atomic order: canonical form, and nothing from an overflowed row
         idx = idx.masked_fill((amb > AMB_SLOTS)[:, None], _RATE_EMPTY).sort(dim=1).values
     return flips, amb, idx
@@ -563,24 +551,19 @@ def ascent(be, q, lo, hi, x0, f0, q0, iters, values, pairs, free_dims):
     candidate rows do not fit in LDS (the caller then runs the PyTorch loop)."""
     P, K, n0 = x0.shape
     dev = x0.device
-    lo_c = _c(lo, torch.float32, (P, n0), "lo")
-    hi_c = _c(hi, torch.float32, (P, n0), "hi")
+    if tuple(lo.shape) != (P, n0):
+        raise ValueError(f"lo: expected shape {(P, n0)}, got {tuple(lo.shape)}")
+    kw, _keep = _query_kw(be, q, lo, hi, None, values, pairs)
     x0_c = _c(x0, torch.float32, (P, K, n0), "x0")
     f0_c = _c(f0, torch.float32, (P, K), "f0")
     q0_c = _c(q0, torch.int32, (P, K), "q0")
-    V = values.shape[0]
-    Pp = pairs.shape[0]
-    values_c = _c(values, torch.int64, None, "values")
-    pairs_c = _c(pairs, torch.int64, (Pp, 2), "pairs")
     found = torch.zeros(P, dtype=torch.uint8, device=dev)
     wx = torch.zeros(P, n0, dtype=torch.float32, device=dev)
     wxp = torch.zeros(P, n0, dtype=torch.float32, device=dev)
     if P == 0:
         return found.bool(), wx, wxp
-    ok = ext().ascent(_net(be), be.flat.data_ptr(), lo_c.data_ptr(), hi_c.data_ptr(), x0_c.data_ptr(),
-                      f0_c.data_ptr(), q0_c.data_ptr(), P, K, int(iters), V, list(q.pa_idx), values_c.data_ptr(),
-                      Pp, pairs_c.data_ptr(), [int(d) for d in free_dims], found.data_ptr(), wx.data_ptr(),
-                      wxp.data_ptr(), _stream(dev))
+    ok = ext().ascent(_net(be), **kw, **_ptrs(x0=x0_c, f0=f0_c, q0=q0_c, found=found, wit_x=wx, wit_xp=wxp), K=K,
+                      iters=int(iters), free=[int(d) for d in free_dims])
     if not ok:
         return None
     return found.bool(), wx, wxp
@@ -595,14 +578,9 @@ def falsify(be, q, lo, hi, pids, values, pairs, seed, n_samples, n_local, walk_k
     network shape is not supported by the kernel (the caller keeps the PyTorch path)."""
     P, n0 = lo.shape
     dev = lo.device
-    lo_c = _c(lo, torch.float32, (P, n0), "lo")
-    hi_c = _c(hi, torch.float32, (P, n0), "hi")
-    pids_c = _c(pids, torch.int64, (P,), "pids")
-    V = values.shape[0]
     Pp = pairs.shape[0]
-    values_c = _c(values, torch.int64, None, "values")
-    pairs_c = _c(pairs, torch.int64, (Pp, 2), "pairs")
-    if values_c.numel() != V * len(q.pa_idx):
+    kw, t = _query_kw(be, q, lo, hi, pids, values, pairs)
+    if t["values"].numel() != kw["V"] * len(q.pa_idx):
         raise ValueError("values: expected [V, n_pa]")
     found = torch.zeros(P, dtype=torch.uint8, device=dev)
     wx = torch.zeros(P, n0, dtype=torch.float32, device=dev)
@@ -610,12 +588,10 @@ def falsify(be, q, lo, hi, pids, values, pairs, seed, n_samples, n_local, walk_k
     how = torch.zeros(P, dtype=torch.int8, device=dev)
     if P == 0 or Pp == 0 or n_samples <= 0:
         return found.bool(), wx, wxp, how
-    ok = ext().falsify(_net(be), be.flat.data_ptr(), lo_c.data_ptr(), hi_c.data_ptr(), pids_c.data_ptr(), P,
-                       int(n_samples), int(n_local), int(seed) & 0xFFFFFFFF, V, list(q.pa_idx), values_c.data_ptr(),
-                       Pp, pairs_c.data_ptr(), int(walk_k), int(walk_steps), int(k_starts), int(iters),
-                       [int(d) for d in free_dims], found.data_ptr(), wx.data_ptr(), wxp.data_ptr(), how.data_ptr(),
-                       _stream(dev), list(q.ra_idx) if q.relaxed else [], int(q.tau) if q.relaxed else 0,
-                       int(dseed) & 0xFFFFFFFF)
+    ok = ext().falsify(_net(be), **kw, **_ptrs(found=found, wit_x=wx, wit_xp=wxp, how=how), n_samples=int(n_samples),
+                       n_local=int(n_local), seed=int(seed) & 0xFFFFFFFF, walk_k=int(walk_k),
+                       walk_steps=int(walk_steps), K=int(k_starts), iters=int(iters),
+                       free=[int(d) for d in free_dims], dseed=int(dseed) & 0xFFFFFFFF)
     if not ok:
         return None
     return found.bool(), wx, wxp, how
@@ -721,21 +697,39 @@ def beta_batched_fits(be) -> bool:
     return bool(ext().beta_batched_fits(_net(be)))
 
 
-def _rx_args(rx, R, n0):
-    """(ramask, plo, phi, gtie [R, 2, n0] or None, tau) of a relaxed level's ``rx`` tuple."""
-    ramask, plo_c, phi_c, gt, tau = 0, None, None, None, 0.0
+def _beta_rows(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, rx, osg):
+    """The rows of one beta level: ``(keywords, tensors)`` of the ``BetaArgs`` inputs the beta bindings
+    share -- node boxes, PA dims and values, partition bounds and phases of both copies, the
+    orientations, a relaxed level's ``rx`` tuple as ramask / plo / phi / gtie ([R, 2, n0], the tie's
+    multipliers in / out) / tau, R and the stream.  The checked contiguous ``tensors`` (same keys)
+    must stay alive until the launch is enqueued."""
+    R, n0 = lo.shape
+    NH = be.n_hidden
+    npa = len(pa)
+    t = dict(flat=be.flat, lo=_c(lo, torch.float32, (R, n0), "lo"), hi=_c(hi, torch.float32, (R, n0), "hi"),
+             va=_c(va, torch.float32, (R, npa), "va"), vb=_c(vb, torch.float32, (R, npa), "vb"))
+    for x, nm in ((LBA, "LBA"), (UBA, "UBA"), (LBB, "LBB"), (UBB, "UBB")):
+        t[nm] = _c(x, torch.float32, (R, NH), nm)
+    t.update(phA=_c(phA, torch.int8, (R, NH), "phA"), phB=_c(phB, torch.int8, (R, NH), "phB"), plo=None, phi=None,
+             gtie=None, osg=None if osg is None else _c(osg, torch.int8, (R,), "osg"))
+    ramask, tau = 0, 0.0
     if rx is not None:          # relaxed: copy B's RA dims over [plo, phi]
         for d in torch.nonzero(rx[0].cpu()).flatten().tolist():
             ramask |= 1 << int(d)
-        plo_c = _c(rx[1], torch.float32, (R, n0), "plo")
-        phi_c = _c(rx[2], torch.float32, (R, n0), "phi")
+        t["plo"] = _c(rx[1], torch.float32, (R, n0), "plo")
+        t["phi"] = _c(rx[2], torch.float32, (R, n0), "phi")
         if len(rx) > 3 and rx[4] is not None:       # the tau tie's multipliers (in / out)
             tau = float(rx[3])
             for x, nm in ((rx[4], "gP"), (rx[5], "gM")):
                 if tuple(x.shape) != (R, n0) or x.dtype != torch.float32:
                     raise ValueError(f"{nm}: expected float32 [{R}, {n0}]")
-            gt = torch.stack([rx[4], rx[5]], 1).contiguous()       # [R, 2, n0]
-    return ramask, plo_c, phi_c, gt, tau
+            t["gtie"] = torch.stack([rx[4], rx[5]], 1).contiguous()
+    kw = dict(_ptrs(**t), R=R, pa=[int(d) for d in pa], ramask=int(ramask), tau=tau, stream=_stream(lo.device))
+    return kw, t
+
+
+def _beta_steps(iters, lr_a, lr_b, lr_t, decay):
+    return dict(iters=int(iters), lr_a=float(lr_a), lr_b=float(lr_b), lr_t=float(lr_t), decay=float(decay))
 
 
 def beta_opt16(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, beA, beB, t, iters, lr_a, lr_b, lr_t,
@@ -747,19 +741,12 @@ def beta_opt16(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, b
     R, n0 = lo.shape
     NH = be.n_hidden
     dev = lo.device
-    npa = len(pa)
     if list(pa) != sorted(pa):
         raise ValueError("beta_opt16: PA dims must be increasing")
     if not beta_batched_fits(be):
         raise RuntimeError("fa_beta_opt16_kernel: network not supported by the batched beta optimiser")
     f32 = dict(dtype=torch.float32, device=dev)
-    lo_c = _c(lo, torch.float32, (R, n0), "lo")
-    hi_c = _c(hi, torch.float32, (R, n0), "hi")
-    va_c = _c(va, torch.float32, (R, npa), "va")
-    vb_c = _c(vb, torch.float32, (R, npa), "vb")
-    bnd = [_c(x, torch.float32, (R, NH), nm) for x, nm in ((LBA, "LBA"), (UBA, "UBA"), (LBB, "LBB"), (UBB, "UBB"))]
-    pA = _c(phA, torch.int8, (R, NH), "phA")
-    pB = _c(phB, torch.int8, (R, NH), "phB")
+    kw, keep = _beta_rows(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, rx, osg)
     for x, nm in ((alA, "alA"), (alB, "alB"), (beA, "beA"), (beB, "beB")):
         if tuple(x.shape) != (R, NH) or x.dtype != torch.float32:
             raise ValueError(f"{nm}: expected float32 [{R}, {NH}]")
@@ -767,18 +754,14 @@ def beta_opt16(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, b
         raise ValueError("t: expected float32 [R]")
     par = torch.stack([alA, alB, beA, beB], 1).contiguous()
     t_o = t.clone().contiguous()
-    ramask, plo_c, phi_c, gt, tau = _rx_args(rx, R, n0)
-    osg_c = None if osg is None else _c(osg, torch.int8, (R,), "osg")
+    gt = keep["gtie"]
     pgsum = torch.zeros(R, 4, NH, **f32)
     pgn = torch.zeros(R, **f32)
     if R:
         scratch = torch.empty(max(int(ext().beta_opt16_scratch(_net(be), R)), 1), **f32)
-        rc = ext().beta_opt16(_net(be), be.flat.data_ptr(), R, [int(d) for d in pa], lo_c.data_ptr(), hi_c.data_ptr(),
-                              va_c.data_ptr(), vb_c.data_ptr(), *[x.data_ptr() for x in bnd], pA.data_ptr(),
-                              pB.data_ptr(), par.data_ptr(), t_o.data_ptr(), scratch.data_ptr(), int(iters),
-                              float(lr_a), float(lr_b), float(lr_t), float(decay), int(bool(beta_pos)), int(pgap),
-                              int(ramask), _ptr(plo_c), _ptr(phi_c), _ptr(gt), float(tau), _ptr(osg_c),
-                              pgsum.data_ptr(), pgn.data_ptr(), _stream(dev))
+        rc = ext().beta_opt16(_net(be), **kw, **_ptrs(par=par, t=t_o, scratch=scratch, pgsum=pgsum, pgn=pgn),
+                              **_beta_steps(iters, lr_a, lr_b, lr_t, decay), beta_pos=int(bool(beta_pos)),
+                              flags=(int(pgap) & 3) << 1)
         if rc != 0:
             raise RuntimeError(f"fa_beta_opt16_kernel launch failed ({rc})")
     return par, t_o, (None if gt is None else gt[:, 0]), (None if gt is None else gt[:, 1]), pgsum, pgn
@@ -821,19 +804,12 @@ def beta_feas(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, t,
     R, n0 = lo.shape
     NH = be.n_hidden
     dev = lo.device
-    npa = len(pa)
     if list(pa) != sorted(pa):
         raise ValueError("beta_feas: PA dims must be increasing")
     two_phase = bool(batched) or proposal is not None
     if two_phase and not beta_batched_fits(be):
         raise RuntimeError("fa_beta_opt16_kernel: network not supported by the batched beta optimiser")
-    lo_c = _c(lo, torch.float32, (R, n0), "lo")
-    hi_c = _c(hi, torch.float32, (R, n0), "hi")
-    va_c = _c(va, torch.float32, (R, npa), "va")
-    vb_c = _c(vb, torch.float32, (R, npa), "vb")
-    bnd = [_c(x, torch.float32, (R, NH), nm) for x, nm in ((LBA, "LBA"), (UBA, "UBA"), (LBB, "LBB"), (UBB, "UBB"))]
-    pA = _c(phA, torch.int8, (R, NH), "phA")
-    pB = _c(phB, torch.int8, (R, NH), "phB")
+    kw, keep = _beta_rows(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, rx, osg)
     for x, nm in ((alA, "alA"), (alB, "alB")):
         if tuple(x.shape) != (R, NH) or x.dtype != torch.float32:
             raise ValueError(f"{nm}: expected float32 [{R}, {NH}]")
@@ -841,8 +817,7 @@ def beta_feas(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, t,
     par = torch.stack([alA, alB, z, z], 1).contiguous()
     t_c = _c(t, torch.float32, (R,), "t").clone()
     bnd_o = _c(bound, torch.float64, (R,), "bound").clone()
-    ramask, plo_c, phi_c, gt, tau = _rx_args(rx, R, n0)
-    osg_c = None if osg is None else _c(osg, torch.int8, (R,), "osg")
+    gt = keep["gtie"]
     fval = torch.full((R,), float("nan"), dtype=torch.float64, device=dev)
     scratch, fpar, fgt = _feas_buffers(be, R, n0, NH, gt is not None, two_phase, dev)
     mode = 1 if batched else 0
@@ -852,12 +827,9 @@ def beta_feas(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, t,
         if gt is not None:
             fgt = _c(proposal[1], torch.float32, (R, 2, n0), "fgt").clone()
     if R:
-        rc = ext().beta_feas(_net(be), be.flat.data_ptr(), _beta_wt(be).data_ptr(), R, [int(d) for d in pa],
-                             lo_c.data_ptr(), hi_c.data_ptr(), va_c.data_ptr(), vb_c.data_ptr(),
-                             *[x.data_ptr() for x in bnd], pA.data_ptr(), pB.data_ptr(), par.data_ptr(),
-                             t_c.data_ptr(), scratch.data_ptr(), int(iters), float(lr[0]), float(lr[1]), float(lr[2]),
-                             float(decay), bnd_o.data_ptr(), int(ramask), _ptr(plo_c), _ptr(phi_c), _ptr(gt),
-                             float(tau), _ptr(osg_c), _ptr(fpar), _ptr(fgt), fval.data_ptr(), mode, _stream(dev))
+        rc = ext().beta_feas(_net(be), **kw, **_beta_steps(iters, lr[0], lr[1], lr[2], decay), mode=mode,
+                             **_ptrs(wt=_beta_wt(be), par=par, t=t_c, scratch=scratch, bound=bnd_o, fpar=fpar, fgt=fgt,
+                                     fval=fval))
         if rc != 0:
             raise RuntimeError(f"beta_feas launch failed ({rc})")
     closed = torch.isinf(bnd_o) & (bnd_o > 0) & ~(torch.isinf(bound) & (bound > 0))
@@ -884,17 +856,11 @@ def beta_level(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, b
     R, n0 = lo.shape
     NH = be.n_hidden
     dev = lo.device
-    npa = len(pa)
     if list(pa) != sorted(pa):
         raise ValueError("beta_level: PA dims must be increasing")
     f32 = dict(dtype=torch.float32, device=dev)
-    lo_c = _c(lo, torch.float32, (R, n0), "lo")
-    hi_c = _c(hi, torch.float32, (R, n0), "hi")
-    va_c = _c(va, torch.float32, (R, npa), "va")
-    vb_c = _c(vb, torch.float32, (R, npa), "vb")
-    bnd = [_c(x, torch.float32, (R, NH), nm) for x, nm in ((LBA, "LBA"), (UBA, "UBA"), (LBB, "LBB"), (UBB, "UBB"))]
-    pA = _c(phA, torch.int8, (R, NH), "phA")
-    pB = _c(phB, torch.int8, (R, NH), "phB")
+    kw, keep = _beta_rows(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, rx, osg)
+    gt = keep["gtie"]
     for x, nm in ((alA, "alA"), (alB, "alB"), (beA, "beA"), (beB, "beB")):
         if tuple(x.shape) != (R, NH) or x.dtype != torch.float32:
             raise ValueError(f"{nm}: expected float32 [{R}, {NH}]")
@@ -918,36 +884,25 @@ def beta_level(be, lo, hi, pa, va, vb, LBA, UBA, LBB, UBB, phA, phB, alA, alB, b
     xstar = torch.empty(R, n0, **f32)
     binit = torch.empty(R, 2, **f32)
     xpstar = torch.empty(R, n0, **f32)
-    ramask, plo_c, phi_c, gt, tau = _rx_args(rx, R, n0)
-    osg_c = None if osg is None else _c(osg, torch.int8, (R,), "osg")
     if batched_feas and gt is not None:
         fgt = torch.empty(R, 2, n0, **f32)
     if R:
-        def launch(n_it, flags, lra, lrb, lrt, two_phase=False):
-            args = (_net(be), be.flat.data_ptr(), _beta_wt(be).data_ptr(), R, [int(d) for d in pa],
-                    lo_c.data_ptr(), hi_c.data_ptr(), va_c.data_ptr(), vb_c.data_ptr(),
-                    *[x.data_ptr() for x in bnd], pA.data_ptr(), pB.data_ptr(), par.data_ptr(),
-                    t.data_ptr(), scratch.data_ptr(), int(n_it), float(lra), float(lrb), float(lrt),
-                    float(decay), int(lookahead), int(bool(beta_pos)), flags, bound.data_ptr(),
-                    split.data_ptr(), xstar.data_ptr(), binit.data_ptr(), int(ramask), _ptr(plo_c),
-                    _ptr(phi_c), xpstar.data_ptr(), _ptr(gt), float(tau), _ptr(osg_c))
-            if two_phase:
-                return ext().beta_level16(*args, pgsum.data_ptr(), pgn.data_ptr(), _stream(dev))
-            return ext().beta_level(*args, _stream(dev))
-
-        rc = launch(iters, flags, lr_a, lr_b, lr_t, two_phase=bool(batched))
-        if rc == 0 and batched_feas:
-            # the two-phase infeasibility pass: proposals on MFMA, the rigorous decision per node
-            fl = feas_lr or (lr_a, lr_b, lr_t)
-            rc = ext().beta_feas(_net(be), be.flat.data_ptr(), _beta_wt(be).data_ptr(), R, [int(d) for d in pa],
-                                 lo_c.data_ptr(), hi_c.data_ptr(), va_c.data_ptr(), vb_c.data_ptr(),
-                                 *[x.data_ptr() for x in bnd], pA.data_ptr(), pB.data_ptr(), par.data_ptr(),
-                                 t.data_ptr(), scratch.data_ptr(), int(feas_iters), float(fl[0]), float(fl[1]),
-                                 float(fl[2]), float(decay), bound.data_ptr(), int(ramask), _ptr(plo_c), _ptr(phi_c),
-                                 _ptr(gt), float(tau), _ptr(osg_c), fpar.data_ptr(), _ptr(fgt), 0, 1, _stream(dev))
-        elif rc == 0 and feas_iters > 0:
-            # the infeasibility pass (bit 3) on the nodes left open: only their bounds can change
-            rc = launch(feas_iters, beta_flags(False, 0, feas=True), *(feas_lr or (lr_a, lr_b, lr_t)))
+        net = _net(be)
+        kw.update(_ptrs(wt=_beta_wt(be), par=par, t=t, scratch=scratch, bound=bound, split=split, xstar=xstar,
+                        binit=binit, xpstar=xpstar),
+                  **_beta_steps(iters, lr_a, lr_b, lr_t, decay), lookahead=int(lookahead),
+                  beta_pos=int(bool(beta_pos)), flags=flags)
+        if batched:
+            rc = ext().beta_level16(net, **kw, **_ptrs(pgsum=pgsum, pgn=pgn))
+        else:
+            rc = ext().beta_level(net, **kw)
+        if rc == 0 and feas_iters > 0:
+            # the infeasibility pass on the nodes left open: only their bounds can change
+            fkw = {**kw, **_beta_steps(feas_iters, *(feas_lr or (lr_a, lr_b, lr_t)), decay)}
+            if batched_feas:        # in two phases: proposals on MFMA, the rigorous decision per node
+                rc = ext().beta_feas(net, **fkw, **_ptrs(fpar=fpar, fgt=fgt), mode=1)
+            else:                   # per node (bit 3 of the flags)
+                rc = ext().beta_level(net, **{**fkw, "flags": beta_flags(False, 0, feas=True)})
         if rc != 0:
             raise RuntimeError(f"fa_beta_kernel launch failed ({rc}): network not supported by the beta kernel")
         if gt is not None:

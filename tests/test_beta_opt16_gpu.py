@@ -332,11 +332,11 @@ def test_second_phase_is_neutral_without_primal_sums(cuda):
     xstar = torch.empty(R, n0, device=cuda)
     binit = torch.empty(R, 2, device=cuda)
     xpstar = torch.empty(R, n0, device=cuda)
-    rc = ext().beta_level(hip._net(be), be.flat.data_ptr(), hip._beta_wt(be).data_ptr(), R, list(pa),
-                          *[x.data_ptr() for x in ins], par.data_ptr(), tt.data_ptr(), scratch.data_ptr(), 3,
-                          LR["lr_a"], LR["lr_b"], LR["lr_t"], 1.0, 0, 1, 1, bound.data_ptr(), split.data_ptr(),
-                          xstar.data_ptr(), binit.data_ptr(), 0, 0, 0, xpstar.data_ptr(), 0, 0.0, 0,
-                          torch.cuda.current_stream(cuda).cuda_stream)
+    kw, _ = hip._beta_rows(be, ins[0], ins[1], pa, *ins[2:], None, None)
+    rc = ext().beta_level(hip._net(be), **kw, **hip._ptrs(wt=hip._beta_wt(be), par=par, t=tt, scratch=scratch,
+                                                          bound=bound, split=split, xstar=xstar, binit=binit,
+                                                          xpstar=xpstar),
+                          iters=3, **LR, decay=1.0, lookahead=0, beta_pos=1, flags=1)
     torch.cuda.synchronize()
     assert rc == 0
     assert torch.equal(bound.cpu(), lg.bound.cpu())

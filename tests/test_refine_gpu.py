@@ -224,10 +224,7 @@ def test_fused_refine_crown_equals_refine_then_crown(cuda, n0, hidden):
     L_, H_ = lo.to(cuda), hi.to(cuda)
     two = gpu.bounds(L_, H_, mode="symbolic", crown=True, refine=True)
     one = gpu.bounds(L_, H_, mode="symbolic", keep_layers=True)
-    ext().refine_crown(H._net(gpu), gpu.flat.data_ptr(), L_.contiguous().data_ptr(), H_.contiguous().data_ptr(), 0,
-                       L_.shape[0], one.out_lb.data_ptr(), one.out_ub.data_ptr(), one.Lc.data_ptr(), one.L0.data_ptr(),
-                       one.Le.data_ptr(), one.Uc.data_ptr(), one.U0.data_ptr(), one.Ue.data_ptr(),
-                       one.lay_lb_full.data_ptr(), one.lay_ub_full.data_ptr(), H._stream(cuda))
+    ext().refine_crown(H._net(gpu), **H._bound_kw(gpu, L_, H_, None, one, one.lay_lb_full, one.lay_ub_full)[0])
     torch.cuda.synchronize()
     scale = float((two.out_ub - two.out_lb).abs().max().cpu() + two.out_ub.abs().max().cpu() + 1e-3)
     assert torch.allclose(one.out_lb, two.out_lb, rtol=1e-4, atol=1e-4 * scale)
@@ -337,10 +334,7 @@ def test_global_weight_refine_bitwise_equals_staged(cuda, monkeypatch, mode):
         if mode == "refine":
             H.refine(gpu, L_, H_, r)
         else:
-            ext().refine_crown(H._net(gpu), gpu.flat.data_ptr(), L_.contiguous().data_ptr(),
-                               H_.contiguous().data_ptr(), 0, L_.shape[0], r.out_lb.data_ptr(), r.out_ub.data_ptr(),
-                               r.Lc.data_ptr(), r.L0.data_ptr(), r.Le.data_ptr(), r.Uc.data_ptr(), r.U0.data_ptr(),
-                               r.Ue.data_ptr(), r.lay_lb_full.data_ptr(), r.lay_ub_full.data_ptr(), H._stream(cuda))
+            ext().refine_crown(H._net(gpu), **H._bound_kw(gpu, L_, H_, None, r, r.lay_lb_full, r.lay_ub_full)[0])
         torch.cuda.synchronize()
         outs.append([r.out_lb, r.out_ub, r.Lc, r.Uc, r.lay_lb_full, r.lay_ub_full])
     for a, b in zip(*outs):
@@ -367,10 +361,7 @@ def test_shaped_refine_kernel_is_bitwise_the_generic_one(cuda, monkeypatch, n0, 
         monkeypatch.setenv("FAIRIFY_REFINE_SHAPED", shaped)
         a = gpu.bounds(L_, H_, mode="symbolic", crown=True, refine=True)
         f = gpu.bounds(L_, H_, mode="symbolic", keep_layers=True)
-        ext().refine_crown(H._net(gpu), gpu.flat.data_ptr(), L_.contiguous().data_ptr(), H_.contiguous().data_ptr(),
-                           0, L_.shape[0], f.out_lb.data_ptr(), f.out_ub.data_ptr(), f.Lc.data_ptr(),
-                           f.L0.data_ptr(), f.Le.data_ptr(), f.Uc.data_ptr(), f.U0.data_ptr(), f.Ue.data_ptr(),
-                           f.lay_lb_full.data_ptr(), f.lay_ub_full.data_ptr(), H._stream(cuda))
+        ext().refine_crown(H._net(gpu), **H._bound_kw(gpu, L_, H_, None, f, f.lay_lb_full, f.lay_ub_full)[0])
         b = gpu.bounds(L_, H_, mode="backward")
         torch.cuda.synchronize()
         outs.append((a, f, b))
