@@ -18,6 +18,12 @@ which gives
 
 With ``check_unsat`` the UNSAT partitions are sampled too: an exact flip inside one contradicts
 the prover and raises :class:`SoundnessError` with the confirmed pair.
+
+With ``certify`` every partition that is sampled is also *counted* by the branch-and-bound of
+``engine/count.py``: ``bounds.csv`` carries its ``fair / unfair / open`` volumes, and
+``certified_lower = sum unfair / W`` and ``certified_upper = sum (unfair + open) / W`` (an UNSAT
+partition of the verify run contributes ``fair = w`` uncounted) bound the domain-wide rate with
+certainty from both sides.
 """
 from __future__ import annotations
 
@@ -31,6 +37,7 @@ import numpy as np
 import torch
 
 from .. import presets
+from ..engine.count import LEAF_POINTS, NODE_BUDGET, count_partitions, witness_pair
 from ..engine.rate import first_exact_pair, measure_partitions
 from ..models.zoo import get_model
 from ..ops.backend import Backend
@@ -39,8 +46,10 @@ from .causal import _z
 from .hybrid import NOT_ATTEMPTED, V_SAT, V_UNKNOWN, V_UNSAT, VerdictTable
 
 CHUNK = 8192
+POOL_NODES = 1 << 24     # certify: partitions per chunk x node_budget (256 partitions at the default budget)
 _NAMES = {V_SAT: "sat", V_UNSAT: "unsat", V_UNKNOWN: "unknown", NOT_ATTEMPTED: "not_attempted"}
 CSV_HEADER = ["Partition_ID", "grid_id", "verdict", "samples", "flips", "rate"]
+BOUNDS_HEADER = ["Partition_ID", "grid_id", "verdict", "weight", "fair", "unfair", "open", "nodes", "lower", "upper"]
 
 
 class SoundnessError(RuntimeError):
@@ -131,13 +140,60 @@ def measure_grid(grid, q, be: Backend, order: np.ndarray, table: Optional[Verdic
     return out, verdict, samples, flips
 
 
+def certify_grid(grid, q, be: Backend, order: np.ndarray, table: Optional[VerdictTable] = None,
+                 node_budget: int = NODE_BUDGET, leaf_points: int = LEAF_POINTS, check_unsat: bool = False):
+    """Count the partitions ``order`` (grid ids) of ``grid`` that :func:`measure_grid` samples, in
+    chunks whose pools stay below ``POOL_NODES`` nodes (a partition's counts do not depend on its
+    chunk).  Returns the certified summary keys and the ``bounds.csv`` rows (without the
+    header).  An UNSAT partition is not counted (``fair = w``) unless ``check_unsat``; then unfair
+    volume inside one raises :class:`SoundnessError` with an exactly confirmed pair.  A SAT partition
+    that counts ``unfair == 0`` and ``open == 0`` contradicts the verify run's confirmed pair and
+    raises ``RuntimeError``."""
+    n = len(order)
+    verdict = np.full(n, NOT_ATTEMPTED, dtype=np.int8) if table is None else table.table[order]
+    rows = []
+    chunk = max(1, min(CHUNK, POOL_NODES // max(1, int(node_budget))))
+    for c0 in range(0, n, chunk):
+        ids = order[c0:c0 + chunk]
+        lo_np, hi_np = grid.decode(ids)
+        wts = stratum_weights(q, lo_np, hi_np)
+        v = verdict[c0:c0 + chunk]
+        four = np.zeros((len(ids), 4), dtype=object)
+        four[:, 0] = wts
+        take = np.nonzero((v != V_UNSAT) | check_unsat)[0]
+        if take.size:
+            pids = torch.from_numpy(ids[take]).to(be.device)
+            lo_t = torch.from_numpy(lo_np[take]).to(be.device, torch.float32)
+            hi_t = torch.from_numpy(hi_np[take]).to(be.device, torch.float32)
+            r = count_partitions(be, q, lo_t, hi_t, pids, node_budget, leaf_points, witness_for=v[take] == V_UNSAT)
+            for j, k in enumerate(take):
+                four[k] = [int(r.fair[j]), int(r.unfair[j]), int(r.open[j]), int(r.nodes[j])]
+                if v[k] == V_UNSAT and r.unfair[j] > 0:
+                    x, xp = witness_pair(be.mlp, q, *r.witness[j])
+                    raise SoundnessError(int(ids[k]), x, xp)
+                if v[k] == V_SAT and r.unfair[j] == 0 and r.open[j] == 0:
+                    raise RuntimeError(f"partition with grid id {int(ids[k])} is SAT in the verify results, but "
+                                       f"every one of its {wts[k]} profiles counts as fair")
+        for k in range(len(ids)):
+            f, u, o, nodes = four[k]
+            rows.append([c0 + k + 1, int(ids[k]), _NAMES[int(v[k])], wts[k], f, u, o, nodes,
+                         repr(u / wts[k]), repr((u + o) / wts[k])])
+    W = sum(r[3] for r in rows)
+    unfair, open_ = sum(r[5] for r in rows), sum(r[6] for r in rows)
+    out = {"certified_lower": (unfair / W) if W else 0.0, "certified_upper": ((unfair + open_) / W) if W else 1.0,
+           "certified_exact": open_ == 0, "count_nodes": sum(r[7] for r in rows)}
+    return out, rows
+
+
 def measure_preset(preset: str, model: str, results: Optional[str] = None, n_samples: int = 1000, seed: int = 0,
                    max_partitions: Optional[int] = None, check_unsat: bool = False, weights: str = "zoo",
                    device: str = "cpu", out_dir: Optional[str] = None, conf: float = 0.95,
-                   resolve: bool = True) -> Dict:
+                   resolve: bool = True, certify: bool = False, node_budget: int = NODE_BUDGET,
+                   leaf_points: int = LEAF_POINTS) -> Dict:
     """Measure ``model`` on the grid of ``preset`` in the seeded processing order (the first
     ``max_partitions`` of it); ``results``: the directory of a verify run (``<model>.csv``).  Writes
-    ``rate.csv`` / ``rate.json`` to ``out_dir`` and returns the summary."""
+    ``rate.csv`` / ``rate.json`` to ``out_dir`` and returns the summary.  ``certify``: also count the
+    sampled partitions (:func:`certify_grid`), write ``bounds.csv`` and report the certified bounds."""
     pre = presets.get(preset)
     grid = pre.grid(seed=seed)
     q = pre.resolved()
@@ -153,6 +209,10 @@ def measure_preset(preset: str, model: str, results: Optional[str] = None, n_sam
     summary, verdict, samples, flips = measure_grid(grid, q, be, order, table, n_samples, seed, check_unsat, conf,
                                                     resolve)
     out.update(summary)
+    bounds = None
+    if certify:
+        cert, bounds = certify_grid(grid, q, be, order, table, node_budget, leaf_points, check_unsat)
+        out.update(cert)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "rate.csv"), "w", newline="") as fp:
@@ -164,4 +224,9 @@ def measure_preset(preset: str, model: str, results: Optional[str] = None, n_sam
                              repr(int(flips[k]) / s) if s else "0.0"])
         with open(os.path.join(out_dir, "rate.json"), "w") as fp:
             json.dump(out, fp, indent=2)
+        if bounds is not None:
+            with open(os.path.join(out_dir, "bounds.csv"), "w", newline="") as fp:
+                wr = csv.writer(fp)
+                wr.writerow(BOUNDS_HEADER)
+                wr.writerows(bounds)
     return out

@@ -6,6 +6,7 @@
     python -m fairify_amd.cli zoo [--import-dir /path/to/models]
     python -m fairify_amd.cli analyze --preset experiment/AC-3 --model AC-3 --fairer AC-3 ...
     python -m fairify_amd.cli measure --preset src/GC-age --model GC-1 --results results/gc --out results/gc-rate
+    python -m fairify_amd.cli measure --preset src/GC-age --model GC-1 --certify [--node-budget N] [--leaf-points K]
     python -m fairify_amd.cli repair --model AC-3 --counterexamples results/ac3/counterexamples.csv ...
     python -m fairify_amd.cli export-cex --preset src/AC-sex --model AC-3 --results results/ac
 
@@ -106,7 +107,8 @@ def cmd_measure(args):
 
     out = measure_preset(args.preset, args.model, results=args.results, n_samples=args.samples, seed=args.seed,
                          max_partitions=args.max_partitions, check_unsat=args.check_unsat, weights=args.weights,
-                         device=_device(args.device), out_dir=args.out)
+                         device=_device(args.device), out_dir=args.out, certify=args.certify,
+                         node_budget=args.node_budget, leaf_points=args.leaf_points)
     print(json.dumps(out, indent=2, default=float))
 
 
@@ -264,7 +266,13 @@ def main(argv=None):
                     help="sample the UNSAT partitions too; an exact flip inside one is a prover bug (SoundnessError)")
     ms.add_argument("--weights", default="zoo")
     ms.add_argument("--device", default=None)
-    ms.add_argument("--out", default=None, help="directory for rate.csv / rate.json")
+    ms.add_argument("--certify", action="store_true",
+                    help="count the sampled partitions with the counting branch-and-bound: bounds.csv and "
+                         "certified_lower / certified_upper in rate.json")
+    ms.add_argument("--node-budget", type=int, default=65536, help="--certify: nodes box-tested per partition")
+    ms.add_argument("--leaf-points", type=int, default=1024,
+                    help="--certify: open nodes of at most this many points are enumerated (<= 65536)")
+    ms.add_argument("--out", default=None, help="directory for rate.csv / rate.json (and bounds.csv)")
     ms.set_defaults(fn=cmd_measure)
 
     r = sub.add_parser("repair", help="bias localisation + masked fine-tune / counterexample retraining")

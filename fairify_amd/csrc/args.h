@@ -537,3 +537,71 @@ struct RateArgs {
   int* amb_idx;             // [P, FA_RATE_SLOTS] their sample indices, any order; complete iff amb <= slots
   int split;                // workgroups per partition (64-profile passes strided over them)
 };
+
+// Counting branch-and-bound (csrc/count.hip, definitions in ops/count.py).  Leaf enumeration: every
+// non-PA lattice point of a leaf box (point s in [0, vol): mixed-radix decode over the non-PA dims in
+// increasing dim order, last dim fastest) classified like a rate profile; per leaf the certain points,
+// the ambiguous ones and up to FA_RATE_SLOTS of their point indices.
+#define FA_COUNT_MAX_VOL 65536
+struct EnumArgs {
+  const float* flat;
+  const float* lo;          // [L, n0] leaf boxes (integral)
+  const float* hi;          // [L, n0]
+  int L;
+  int V;                    // PA assignments
+  int npa;
+  int pa_idx[FA_MAX_PA];
+  const int64_t* values;    // [V, npa]
+  int Pp;                   // valid ordered pairs
+  const int64_t* pairs;     // [Pp, 2]
+  int nra;                  // 0: PA-only query
+  int ra_idx[FA_MAX_RA];
+  int tau;
+  int E;                    // (2 tau + 1)^nra offset vectors (1 when nra == 0)
+  int max_vol;              // the caller's bound of a leaf's volume (<= FA_COUNT_MAX_VOL); a leaf over it
+                            // is not enumerated: cert = -1
+  int* cert;                // [L] certain points
+  int* amb;                 // [L] ambiguous points                      (zero-initialised by the caller)
+  int* amb_idx;             // [L, FA_RATE_SLOTS] their point indices, any order; complete iff amb <= slots
+  int blocks;               // workgroups (leaves strided over them)
+};
+
+// Row expansion and level step of the counting branch-and-bound: node k owns rows k V .. k V + V - 1
+// (its box with the PA dims pinned to values[v]); the counterpart rows are the same rows with every RA
+// dim widened by tau on both sides (relaxed queries only).
+struct CountArgs {
+  int N, n0, V;
+  int npa;
+  int pa_idx[FA_MAX_PA];
+  int nra;
+  int ra_idx[FA_MAX_RA];
+  float tau;
+  const float* lo;          // [N, n0] node boxes
+  const float* hi;
+  const float* values;      // [V, npa]                                  (rows kernel)
+  float* rlo;               // [N V, n0] x rows                          (rows kernel)
+  float* rhi;
+  float* plo;               // [N V, n0] counterpart rows or nullptr     (rows kernel, relaxed)
+  float* phi;
+  // level step
+  const int* part;          // [N] partition of each node
+  const float *lx, *ux;     // [N V] logit bounds of the x rows
+  const float *lxp, *uxp;   // [N V] of the counterpart rows (the x rows' when not relaxed)
+  int Pp;
+  const int64_t* pairs;     // [Pp, 2]
+  const float* score;       // [n0] s_d = sum_j |W_0[d, j]| (fp32)
+  long long leaf_points;    // an OPEN node of at most this volume is a leaf
+  uint8_t* code;            // [N] 0 OPEN, 1 FAIR, 2 UNFAIR
+  long long* fair;          // [P] volumes, added
+  long long* unfair;        // [P]
+  int* child_cnt;           // [P] children per partition, added
+  float* olo;               // child pool [cap, n0]
+  float* ohi;
+  int* opart;               // [cap]
+  int cap;
+  float* leaf_lo;           // leaf list [leaf_cap, n0]
+  float* leaf_hi;
+  int* leaf_part;           // [leaf_cap]
+  int leaf_cap;
+  int* counters;            // [0] children, [1] leaves, [2] nodes that did not fit (must stay 0)
+};

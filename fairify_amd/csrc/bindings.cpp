@@ -32,6 +32,9 @@ extern "C" int fa_forward_launch(const NetDesc& net, FwdArgs a, hipStream_t stre
 extern "C" int fa_sim_launch(const NetDesc& net, SimArgs a, hipStream_t stream);
 extern "C" int fa_sim_shaped(const NetDesc& net);
 extern "C" int fa_rate_launch(const NetDesc& net, RateArgs a, hipStream_t stream);
+extern "C" int fa_count_enum_launch(const NetDesc& net, EnumArgs a, hipStream_t stream);
+extern "C" int fa_count_rows_launch(CountArgs a, hipStream_t stream);
+extern "C" int fa_count_level_launch(CountArgs a, hipStream_t stream);
 extern "C" int fa_ascent_launch(const NetDesc& net, AscentArgs a, hipStream_t stream);
 extern "C" int fa_certify_launch(CertArgs a, hipStream_t stream);
 extern "C" int fa_falsify_launch(const NetDesc& net, FalsifyArgs a, hipStream_t stream);
@@ -401,6 +404,87 @@ PYBIND11_MODULE(_C, m) {
     const int rc = fa_rate_launch(net.d, a, finish(k));
     if (rc == -3) throw std::invalid_argument("rate: shape not covered (layer > 160, inputs > 32, V > 32 or E > 32)");
     ckl(rc, "rate");
+  });
+
+  // counting branch-and-bound (csrc/count.hip).  count_enum: leaf enumeration; amb zero-initialised by
+  // the caller
+  m.def("count_enum", [](const Net& net, py::kwargs kw) {
+    Kw k("count_enum", kw);
+    EnumArgs a{};
+    a.flat = k.need<const float>("flat");
+    a.lo = k.need<const float>("lo");
+    a.hi = k.need<const float>("hi");
+    a.L = k.i("L");
+    a.V = k.i("V");
+    a.npa = dims(k, "pa", a.pa_idx, FA_MAX_PA, "too many PA/RA dims");
+    a.values = k.need<const int64_t>("values");
+    a.Pp = k.i("Pp");
+    a.pairs = k.ptr<const int64_t>("pairs");
+    a.nra = dims(k, "ra", a.ra_idx, FA_MAX_RA, "too many PA/RA dims");
+    a.tau = k.i("tau");
+    a.E = k.i("E");
+    a.max_vol = k.i("max_vol");
+    a.cert = k.need<int>("cert");
+    a.amb = k.need<int>("amb");
+    a.amb_idx = k.need<int>("amb_idx");
+    a.blocks = k.i("blocks");
+    if (a.Pp > 0 && !a.pairs) throw py::type_error("count_enum() missing required keyword argument 'pairs'");
+    const int rc = fa_count_enum_launch(net.d, a, finish(k));
+    if (rc == -3)
+      throw std::invalid_argument(
+          "count_enum: shape not covered (layer > 160, inputs > 32, V > 32, E > 32 or leaf volume > 65536)");
+    ckl(rc, "count_enum");
+  });
+  // the block the row expansion and the level step share
+  auto count_args = [](Kw& k) {
+    CountArgs a{};
+    a.N = k.i("N");
+    a.n0 = k.i("n0");
+    a.V = k.i("V");
+    a.npa = dims(k, "pa", a.pa_idx, FA_MAX_PA, "too many PA/RA dims");
+    a.lo = k.need<const float>("lo");
+    a.hi = k.need<const float>("hi");
+    return a;
+  };
+  m.def("count_rows", [count_args](py::kwargs kw) {
+    Kw k("count_rows", kw);
+    CountArgs a = count_args(k);
+    a.nra = dims(k, "ra", a.ra_idx, FA_MAX_RA, "too many PA/RA dims");
+    a.tau = k.f("tau");
+    a.values = k.need<const float>("values");
+    a.rlo = k.need<float>("rlo");
+    a.rhi = k.need<float>("rhi");
+    a.plo = k.ptr<float>("plo");
+    a.phi = k.ptr<float>("phi");
+    ckl(fa_count_rows_launch(a, finish(k)), "count_rows");
+  });
+  m.def("count_level", [count_args](py::kwargs kw) {
+    Kw k("count_level", kw);
+    CountArgs a = count_args(k);
+    a.part = k.need<const int>("part");
+    a.lx = k.need<const float>("lx");
+    a.ux = k.need<const float>("ux");
+    a.lxp = k.need<const float>("lxp");
+    a.uxp = k.need<const float>("uxp");
+    a.Pp = k.i("Pp");
+    a.pairs = k.ptr<const int64_t>("pairs");
+    a.score = k.need<const float>("score");
+    a.leaf_points = (long long)k.u64("leaf_points");
+    a.code = k.need<uint8_t>("code");
+    a.fair = k.need<long long>("fair");
+    a.unfair = k.need<long long>("unfair");
+    a.child_cnt = k.need<int>("child_cnt");
+    a.olo = k.need<float>("olo");
+    a.ohi = k.need<float>("ohi");
+    a.opart = k.need<int>("opart");
+    a.cap = k.i("cap");
+    a.leaf_lo = k.need<float>("leaf_lo");
+    a.leaf_hi = k.need<float>("leaf_hi");
+    a.leaf_part = k.need<int>("leaf_part");
+    a.leaf_cap = k.i("leaf_cap");
+    a.counters = k.need<int>("counters");
+    if (a.Pp > 0 && !a.pairs) throw py::type_error("count_level() missing required keyword argument 'pairs'");
+    ckl(fa_count_level_launch(a, finish(k)), "count_level");
   });
 
   // returns false if the partition's candidate rows do not fit in LDS (caller keeps PyTorch)

@@ -543,6 +543,143 @@ def rate_counts(be, q, lo, hi, pids, n_samples, seed, values, pairs, split: Opti
     return flips, amb, idx
 
 
+# Workgroups of a leaf list: at least 1 024 (4 per CU), and enough that a workgroup enumerates about
+# _ENUM_POINTS points per staging of W -- leaves of 1 000 points measured 4 - 13 % faster one per
+# workgroup than eight per workgroup (profiles/r12/count/README.md); only small leaves share a workgroup
+_ENUM_BLOCKS = 1024
+_ENUM_POINTS = 1024
+
+
+def _count_shape(be, q, values, pairs, what):
+    """Launch-shape checks of the counting kernels; returns (V, Pp, E)."""
+    from .rate import offset_vectors
+
+    npa = len(q.pa_idx)
+    if values.dim() != 2 or values.shape[1] != npa:
+        raise ValueError(f"values: expected [V, {npa}], got {tuple(values.shape)}")
+    V, Pp = int(values.shape[0]), int(pairs.shape[0])
+    if not 1 <= V <= 32:
+        raise ValueError(f"{what}: {V} PA assignments, the kernels cover 1..32")
+    if Pp and (int(pairs.min()) < 0 or int(pairs.max()) >= V):
+        raise ValueError("pairs: index outside [0, V)")
+    E = int(offset_vectors(q).shape[0])                    # raises over MAX_OFFSETS
+    return V, Pp, E
+
+
+def count_enum(be, q, lo, hi, values, pairs, max_vol: Optional[int] = None, blocks: Optional[int] = None):
+    """Leaf enumeration in one launch (``fa_count_enum_kernel``, definitions in ops/count.py):
+    (certain points [L], ambiguous points [L], ambiguous point indices [L, 32]) int32.  An index row
+    is sorted ascending and padded with INT32_MAX; the row of a leaf with more than 32 ambiguous
+    points is returned all padding.  ``max_vol``: the caller's bound of the leaves' volumes
+    (default: computed from the boxes); ``blocks``: workgroups (every value gives the same outputs)."""
+    from .count import MAX_LEAF_POINTS, free_dims, volumes
+    from .rate import AMB_SLOTS
+
+    L, n0 = lo.shape
+    dev = lo.device
+    if n0 != be.n0:
+        raise ValueError(f"lo: expected [L, {be.n0}], got {tuple(lo.shape)}")
+    lo = _c(lo, torch.float32, (L, n0), "lo")
+    hi = _c(hi, torch.float32, (L, n0), "hi")
+    values = _c(values, torch.int64, None, "values")
+    pairs = _c(pairs, torch.int64, (pairs.shape[0], 2), "pairs")
+    V, Pp, E = _count_shape(be, q, values, pairs, "count_enum")
+    if max([be.n0] + list(be.widths)) > 160 or be.n0 > 32:
+        raise ValueError("count_enum: the kernel covers layers up to 160 wide and up to 32 inputs")
+    if max_vol is None:
+        max_vol = int(volumes(lo, hi, free_dims(q)).max()) if L else 1
+    if not 1 <= int(max_vol) <= MAX_LEAF_POINTS:
+        raise ValueError(f"count_enum: leaf volume {max_vol} outside 1..{MAX_LEAF_POINTS}")
+    if blocks is None:
+        blocks = min(max(L, 1), max(_ENUM_BLOCKS, L * int(max_vol) // _ENUM_POINTS))
+    if L and not 1 <= int(blocks) <= L:
+        raise ValueError(f"count_enum: {blocks} workgroups outside 1..{L}")
+    cert = torch.zeros(L, dtype=torch.int32, device=dev)
+    amb = torch.zeros(L, dtype=torch.int32, device=dev)
+    idx = torch.full((L, AMB_SLOTS), _RATE_EMPTY, dtype=torch.int32, device=dev)
+    if L:
+        ext().count_enum(_net(be), **_ptrs(flat=be.flat, lo=lo, hi=hi, values=values, pairs=pairs if Pp else None,
+                                           cert=cert, amb=amb, amb_idx=idx),
+                         L=L, V=V, pa=list(q.pa_idx), Pp=Pp, ra=list(q.ra_idx) if q.relaxed else [],
+                         tau=int(q.tau) if q.relaxed else 0, E=E, max_vol=int(max_vol), blocks=int(blocks),
+                         stream=_stream(dev))
+        idx = idx.masked_fill((amb > AMB_SLOTS)[:, None], _RATE_EMPTY).sort(dim=1).values
+    return cert, amb, idx
+
+
+def count_rows(be, q, lo, hi, values):
+    """Node boxes [N, n0] -> x rows ``rlo, rhi`` [N V, n0] and counterpart rows ``plo, phi`` (the x
+    rows themselves for a PA-only query) via ``fa_count_rows_kernel`` (ops/count.py:node_rows)."""
+    N, n0 = lo.shape
+    dev = lo.device
+    lo = _c(lo, torch.float32, (N, n0), "lo")
+    hi = _c(hi, torch.float32, (N, n0), "hi")
+    npa = len(q.pa_idx)
+    values = _c(values, torch.float32, None, "values")
+    if values.dim() != 2 or values.shape[1] != npa or values.shape[0] < 1:
+        raise ValueError(f"values: expected [V, {npa}], got {tuple(values.shape)}")
+    if any(not 0 <= d < n0 for d in list(q.pa_idx) + list(q.ra_idx)):
+        raise ValueError("count_rows: PA / RA dim outside the inputs")
+    V = int(values.shape[0])
+    f32 = dict(dtype=torch.float32, device=dev)
+    rlo, rhi = torch.empty(N * V, n0, **f32), torch.empty(N * V, n0, **f32)
+    plo = phi = None
+    if q.relaxed:
+        plo, phi = torch.empty(N * V, n0, **f32), torch.empty(N * V, n0, **f32)
+    if N:
+        ext().count_rows(**_ptrs(lo=lo, hi=hi, values=values, rlo=rlo, rhi=rhi, plo=plo, phi=phi), N=N, n0=n0, V=V,
+                         pa=list(q.pa_idx), ra=list(q.ra_idx) if q.relaxed else [],
+                         tau=float(q.tau) if q.relaxed else 0.0, stream=_stream(dev))
+    return (rlo, rhi, plo, phi) if q.relaxed else (rlo, rhi, rlo, rhi)
+
+
+def count_level(be, q, lo, hi, part, lx, ux, lxp, uxp, pairs, score, leaf_points, fair, unfair, child_cnt,
+                part_checked: bool = False):
+    """Level step of the counting branch-and-bound over ``N`` nodes (``fa_count_level_kernel``):
+    box test, volumes of the FAIR / UNFAIR nodes added to ``fair`` / ``unfair`` [P] int64, children
+    counted into ``child_cnt`` [P] int32.  Returns (class codes [N] uint8, child pool ``clo, chi``
+    [2 N, n0] and ``cpart`` [2 N], leaf list ``llo, lhi`` [N, n0] and ``lpart`` [N], counters [3]
+    int32 on the device: children, leaves, nodes that did not fit); the lists are filled up to the
+    counters, in atomic order.  ``part_checked``: the caller vouches for ``part`` in [0, P) (the level
+    loop's pools come from this kernel; checking them would cost a synchronisation per slice)."""
+    N, n0 = lo.shape
+    dev = lo.device
+    lo = _c(lo, torch.float32, (N, n0), "lo")
+    hi = _c(hi, torch.float32, (N, n0), "hi")
+    part = _c(part, torch.int32, (N,), "part")
+    V = lx.numel() // max(N, 1)
+    t = {k: _c(v, torch.float32, (N * V,), k) for k, v in dict(lx=lx.reshape(-1), ux=ux.reshape(-1),
+                                                                lxp=lxp.reshape(-1), uxp=uxp.reshape(-1)).items()}
+    pairs = _c(pairs, torch.int64, (pairs.shape[0], 2), "pairs")
+    Pp = int(pairs.shape[0])
+    score = _c(score.to(dev), torch.float32, (n0,), "score")
+    P = fair.shape[0]
+    for name, x, dt in (("fair", fair, torch.int64), ("unfair", unfair, torch.int64), ("child_cnt", child_cnt, torch.int32)):
+        if x.dtype != dt or tuple(x.shape) != (P,) or not x.is_contiguous() or x.device != dev:
+            raise ValueError(f"{name}: expected a contiguous [{P}] {dt} tensor on {dev}")
+    if N and not part_checked and (int(part.min()) < 0 or int(part.max()) >= P):
+        raise ValueError("part: partition index outside [0, P)")
+    if N and V < 1:
+        raise ValueError("count_level: no rows")
+    if any(not 0 <= d < n0 for d in q.pa_idx):
+        raise ValueError("count_level: PA dim outside the inputs")
+    if not 1 <= int(leaf_points) < 2 ** 62:
+        raise ValueError(f"count_level: bad leaf size {leaf_points}")
+    f32 = dict(dtype=torch.float32, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    code = torch.empty(N, dtype=torch.uint8, device=dev)
+    clo, chi, cpart = torch.empty(2 * N, n0, **f32), torch.empty(2 * N, n0, **f32), torch.empty(2 * N, **i32)
+    llo, lhi, lpart = torch.empty(N, n0, **f32), torch.empty(N, n0, **f32), torch.empty(N, **i32)
+    counters = torch.zeros(3, **i32)
+    if N:
+        ext().count_level(**_ptrs(lo=lo, hi=hi, part=part, pairs=pairs if Pp else None, score=score, code=code,
+                                  fair=fair, unfair=unfair, child_cnt=child_cnt, olo=clo, ohi=chi, opart=cpart,
+                                  leaf_lo=llo, leaf_hi=lhi, leaf_part=lpart, counters=counters, **t),
+                          N=N, n0=n0, V=V, pa=list(q.pa_idx), Pp=Pp, leaf_points=int(leaf_points), cap=2 * N,
+                          leaf_cap=N, stream=_stream(dev))
+    return code, (clo, chi, cpart), (llo, lhi, lpart), counters
+
+
 def ascent(be, q, lo, hi, x0, f0, q0, iters, values, pairs, free_dims):
     """Lattice coordinate ascent of the residual falsifier in one launch (``fa_ascent_kernel``).
 
