@@ -354,7 +354,11 @@ PYBIND11_MODULE(_C, m) {
   // rows that are points: lo = hi = x; the point kernel, or the interval pass where it does not fit
   m.def("point_bounds", [](const Net& net, py::kwargs kw) {
     Kw k("point_bounds", kw);
-    const BoundArgs a = bound_args(k, OUT, "x", "x");
+    BoundArgs a = bound_args(k, OUT, "x", "x");
+    // optional closed-node skip of the BaB level (args.h): point r belongs to node r % open_mod
+    a.row_open = k.ptr<const uint8_t>("row_open");
+    a.open_mod = k.i("open_mod", 0);
+    if (a.row_open && a.open_mod <= 0) throw std::invalid_argument("point_bounds: row_open needs open_mod > 0");
     const hipStream_t stream = finish(k);
     const int rc = fa_point_try_launch(net.d, a, stream);
     if (rc < 0) ckl(-rc, "point_bounds");

@@ -30,6 +30,19 @@ template <int TM>
 __global__ void __launch_bounds__(FA_THREADS) __attribute__((amdgpu_waves_per_eu(TM == 7 ? 2 : 1))) fa_point_kernel(NetDesc net, BoundArgs a, PointCfg cfg) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x;
+  // BaB level: most nodes of a level are closed, and a workgroup none of whose tiles has an open
+  // point would stage the whole weight block (63 KB for AC-4) to write nothing.  One pass over
+  // row_open for the tiles of its grid-stride loop; the verdict is uniform over the workgroup.
+  if (a.row_open) {
+    const int nw = FA_THREADS / 64;
+    const int ntile = (a.R + 15) >> 4;
+    int any = 0;
+    for (int tile = blockIdx.x * nw + (tid >> 6); tile < ntile; tile += gridDim.x * nw) {
+      const int p = tile * 16 + (tid & 15);
+      any |= p < a.R && a.row_open[p % a.open_mod];
+    }
+    if (!__syncthreads_or(any)) return;
+  }
   // ---- stage the MFMA-operand-order weights + biases (pre-permuted in `flat`) into LDS
   {
     const float4* src = reinterpret_cast<const float4*>(a.flat + net.wperm_off);
