@@ -13,15 +13,17 @@ chunk is decided *together* by a device-resident branch-and-bound over the integ
 * leaves are single lattice points, evaluated exactly — the procedure is complete on the finite
   domain, budgets (nodes per partition, wall clock) turn the remainder into UNKNOWN.
 
-All node bookkeeping is tensor code on the device; the only host round trip per iteration is
-the (tiny) SAT-candidate list.
+All node bookkeeping is tensor code on the device; the only host round trip per iteration is the (tiny)
+SAT-candidate list.  The torch loop here (state ``_TorchSearch``, one function per step) is what the CPU tier
+tests; a HIP device runs csrc/bab_runtime.cpp.  Verdict codes, result record, PA grouping: engine/search.py.
 """
 from __future__ import annotations
 
 import os
 import threading
 import time
-from dataclasses import dataclass, field, replace
+from collections import namedtuple
+from dataclasses import dataclass, replace
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -32,13 +34,13 @@ from ..ops.backend import Backend
 from ..spec import ResolvedQuery
 from ..utils.timer import NULL, StageTimer
 from . import exact
-
-UNKNOWN, SAT, UNSAT, RUNNING = 0, 1, 2, 3
+from .search import (RUNNING, SAT, UNKNOWN, UNSAT, VERDICT_NAMES, BaBResult, Verdicts, clamp_tau,  # noqa: F401
+                     confirm_pairs, halve, pa_groups, pa_table, pool_overflow, solve_pa_groups)
+from .search import pa_table as _pa_table  # noqa: F401  (test modules of the parent commit import it from here)
 
 # process-wide native-runtime counters (diagnostics: tools/diag_shard_diff.py, bench --profile)
 STATS: Dict[str, int] = {"levels": 0, "launches": 0, "cand_overflow_levels": 0}
 _STATS_LOCK = threading.Lock()
-VERDICT_NAMES = {UNKNOWN: "unknown", SAT: "sat", UNSAT: "unsat", RUNNING: "running"}
 
 
 @dataclass
@@ -78,18 +80,6 @@ class BaBConfig:
     escalate_steps: Tuple[Tuple[int, int], ...] = ()
 
 
-@dataclass
-class BaBResult:
-    status: np.ndarray               # [P] int8 verdicts
-    cex_x: np.ndarray                # [P, n0] int64 (valid where SAT)
-    cex_xp: np.ndarray
-    nodes: np.ndarray                # [P] int64 nodes expanded
-    iters: int = 0
-    time: float = 0.0
-    open_left: Optional[np.ndarray] = None   # [P] open nodes left when an UNKNOWN partition stopped
-                                             # (native runtime; the escalation filter's predictor)
-
-
 def refine_level(mode: str, widths) -> int:
     """How the BaB bounds its nodes (BaBConfig.refine): 0 forward symbolic + backward output pass,
     1 with back-substituted hidden-layer bounds between them (csrc/refine.hip), 2 back-substitution
@@ -121,26 +111,29 @@ def refine_on(mode: str, widths) -> bool:
     return refine_level(mode, widths) > 0
 
 
-def pa_groups(q: ResolvedQuery, lo: np.ndarray, hi: np.ndarray) -> List[np.ndarray]:
-    """Row indices of the partitions sharing one protected-attribute range (one group when the
-    chunk's PA ranges are identical, e.g. a PA that the partition size does not split)."""
-    pa = list(q.pa_idx)
-    if len(lo) == 0 or (np.all(lo[:, pa] == lo[:1, pa]) and np.all(hi[:, pa] == hi[:1, pa])):
-        return [np.arange(len(lo))]
-    key = np.concatenate([lo[:, pa], hi[:, pa]], axis=1)
-    _, inv = np.unique(key, axis=0, return_inverse=True)
-    inv = inv.reshape(-1)
-    return [np.nonzero(inv == g)[0] for g in range(int(inv.max()) + 1)]
+# nodes of the torch loop: x boxes, x' boxes (full rows; the x tensors themselves for a PA-only query), partitions
+_Nodes = namedtuple("_Nodes", "lo hi plo phi part")
 
 
-def _pa_table(q: ResolvedQuery, lo: np.ndarray, hi: np.ndarray):
-    """PA assignments shared by all partitions of one PA group (:func:`pa_groups`)."""
-    pa = list(q.pa_idx)
-    assert np.all(lo[:, pa] == lo[:1, pa]) and np.all(hi[:, pa] == hi[:1, pa]), \
-        "internal: one PA table per group (callers split with pa_groups)"
-    values = q.pa_values(lo[0], hi[0])
-    pairs = q.pa_pairs(values)
-    return values, pairs
+class _TorchSearch:
+    """State of the torch loop over one PA group: the PA table, the device status / node counts the loop
+    works on, the FIFO pool (a root per RUNNING partition)."""
+
+    def __init__(self, sol: "BaBSolver", lo_np, hi_np, v: Verdicts, values_np, pairs_np):
+        dev = sol.dev
+        self.values = torch.from_numpy(values_np).to(dev)
+        self.pairs = torch.from_numpy(pairs_np).to(dev)
+        run_idx = np.nonzero(v.status == RUNNING)[0]
+        xlo = torch.from_numpy(lo_np[run_idx]).to(dev, torch.float32)
+        xhi = torch.from_numpy(hi_np[run_idx]).to(dev, torch.float32)
+        xplo, xphi = xlo, xhi
+        if sol.relaxed:
+            xplo, xphi = xlo.clone(), xhi.clone()
+            xplo[:, sol.ra] -= sol.tau
+            xphi[:, sol.ra] += sol.tau
+        self.pool = _Nodes(xlo, xhi, xplo, xphi, torch.from_numpy(run_idx).to(dev))
+        self.status_t = torch.from_numpy(v.status).to(dev)
+        self.nodes_t = torch.zeros(len(v.status), dtype=torch.long, device=dev)
 
 
 class BaBSolver:
@@ -152,15 +145,13 @@ class BaBSolver:
         self.cfg = cfg
         self.dev = backend.device
         self.dead = dead            # optional [P, N_hidden] bool (heuristically pruned nets)
-        n = query.n
         self.pa = torch.tensor(list(query.pa_idx), dtype=torch.long, device=self.dev)
         self.ra = torch.tensor(list(query.ra_idx), dtype=torch.long, device=self.dev)
-        shared = np.ones(n, dtype=bool)
+        shared = np.ones(query.n, dtype=bool)
         shared[list(query.ra_idx)] = False
         self.shared = torch.from_numpy(shared).to(self.dev)     # PA dims are fixed per row -> "shared" ok
         self.relaxed = query.relaxed
         self.tau = float(query.tau)
-        # mlp with dead-masks applied host-side for exact checks (per partition if masked)
 
     # --------------------------------------------------------------------------------------
     def _rows(self, lo: torch.Tensor, hi: torch.Tensor, values: torch.Tensor):
@@ -185,207 +176,160 @@ class BaBSolver:
         return sure, poss & ~sure
 
     # --------------------------------------------------------------------------------------
-    def solve(self, lo_np: np.ndarray, hi_np: np.ndarray, mlp_exact: MLP,
-              init_status: Optional[np.ndarray] = None,
+    def solve(self, lo_np: np.ndarray, hi_np: np.ndarray, mlp_exact: MLP, init_status: Optional[np.ndarray] = None,
               exact_models: Optional[List[MLP]] = None) -> BaBResult:
-        """Decide every partition box ``[lo_np[p], hi_np[p]]``.
-
-        ``mlp_exact`` is the network used for exact confirmation (per-partition nets in
-        ``exact_models`` when heuristic masks are active).
-        """
+        """Decide every partition box ``[lo_np[p], hi_np[p]]``.  ``mlp_exact`` is the network used for exact
+        confirmation (per-partition nets in ``exact_models`` when heuristic masks are active)."""
         t0 = time.time()
         groups = pa_groups(self.q, lo_np, hi_np)
         if len(groups) > 1:
             return self._solve_groups(groups, lo_np, hi_np, mlp_exact, init_status, exact_models, t0)
-        cfg = self.cfg
-        dev = self.dev
-        P, n = lo_np.shape
-        values_np, pairs_np = _pa_table(self.q, lo_np, hi_np)
-        values = torch.from_numpy(values_np).to(dev)
-        pairs = torch.from_numpy(pairs_np).to(dev)
-        V = values.shape[0]
-        status = np.full(P, RUNNING, dtype=np.int8) if init_status is None else init_status.astype(np.int8).copy()
-        cex_x = np.zeros((P, n), dtype=np.int64)
-        cex_xp = np.zeros((P, n), dtype=np.int64)
-        nodes_np = np.zeros(P, dtype=np.int64)
-        if pairs.shape[0] == 0:
-            status[status == RUNNING] = UNSAT   # a single PA value: no x' can differ
-            return BaBResult(status, cex_x, cex_xp, nodes_np, 0, time.time() - t0)
+        values_np, pairs_np = pa_table(self.q, lo_np, hi_np)
+        v = Verdicts(*lo_np.shape, init_status)
+        if pairs_np.shape[0] == 0:
+            return v.close_running(UNSAT).result(t0)    # a single PA value: no x' can differ
         if self.be.hip and os.environ.get("FAIRIFY_TORCH_BAB") != "1":
-            return self._solve_native(lo_np, hi_np, status, values_np, pairs_np, mlp_exact, exact_models, t0)
-
-        dt = torch.float32
-        run_idx = np.nonzero(status == RUNNING)[0]
-        xlo = torch.from_numpy(lo_np[run_idx]).to(dev, dt)
-        xhi = torch.from_numpy(hi_np[run_idx]).to(dev, dt)
-        part = torch.from_numpy(run_idx).to(dev)
-        if self.relaxed:
-            xplo = xlo.clone()
-            xphi = xhi.clone()
-            xplo[:, self.ra] -= self.tau
-            xphi[:, self.ra] += self.tau
-        else:
-            xplo, xphi = xlo, xhi
-        status_t = torch.from_numpy(status).to(dev)
-        nodes_t = torch.zeros(P, dtype=torch.long, device=dev)
-        it = 0
-        while xlo.shape[0] > 0:
-            if time.time() - t0 > cfg.time_budget:
+            return self._solve_native(lo_np, hi_np, v.status, values_np, pairs_np, mlp_exact, exact_models, t0)
+        s, it = _TorchSearch(self, lo_np, hi_np, v, values_np, pairs_np), 0
+        while s.pool.part.shape[0] > 0:
+            if time.time() - t0 > self.cfg.time_budget:
                 break
             it += 1
-            B = min(cfg.batch_nodes, xlo.shape[0])
-            blo, bhi, bpart = xlo[:B], xhi[:B], part[:B]
-            bplo, bphi = (xplo[:B], xphi[:B]) if self.relaxed else (blo, bhi)
-            # drop nodes of partitions that are already decided
-            alive = status_t[bpart] == RUNNING
-            if not bool(alive.all()):
-                blo, bhi, bpart, bplo, bphi = blo[alive], bhi[alive], bpart[alive], bplo[alive], bphi[alive]
-            rest = slice(B, None)
-            if blo.shape[0] == 0:
-                xlo, xhi, part = xlo[rest], xhi[rest], part[rest]
-                if self.relaxed:
-                    xplo, xphi = xplo[rest], xphi[rest]
+            b = self._take_batch(s)
+            if b is None:
                 continue
-            Nn = blo.shape[0]
-            nodes_t.index_add_(0, bpart, torch.ones_like(bpart))
-            dead_rows = None
-            if self.dead is not None:
-                dead_rows = self.dead[bpart].repeat_interleave(V, dim=0)
-            with self.tm("bab.bounds"):
-                rlo, rhi = self._rows(blo, bhi, values)
-                rf = refine_on(self.cfg.refine, self.be.widths)
-                res_x = self.be.bounds(rlo, rhi, mode=cfg.mode, dead=dead_rows, crown=cfg.crown, refine=rf)
-                if self.relaxed:
-                    plo, phi = self._rows(bplo, bphi, values)
-                    res_xp = self.be.bounds(plo, phi, mode=cfg.mode, dead=dead_rows, crown=cfg.crown, refine=rf)
-                else:
-                    res_xp = res_x
-            with self.tm("bab.certify"):
-                dec = self.be.pair_certify(res_x, res_xp, blo, bhi, bplo, bphi, pairs, values, self.pa, self.shared,
-                                           self.relaxed)
-            open_ = dec.open_
-            # ---- candidate vertex pairs (falsification inside BaB)
-            pv = pairs[dec.cand_v]
-            cx = dec.cand_x.clone()
-            cxp = dec.cand_xp.clone()
-            cx[:, self.pa] = values[pv[:, 0]].to(cx.dtype)
-            cxp[:, self.pa] = values[pv[:, 1]].to(cx.dtype)
+            dec = self._bound(s, b)
+            cx, cxp, leaf, sel, found = self._candidates(s, b, dec)
+            found += self._leaves(s, b, torch.nonzero(leaf & sel).flatten(), cx, cxp)
+            if found:
+                rows = torch.cat(found)
+                with self.tm("bab.confirm"):   # in the order found; new SATs go into the device status too
+                    newly = confirm_pairs(v, self.q, lo_np, hi_np, mlp_exact, b.part[rows].cpu().numpy(), cx[rows],
+                                          cxp[rows], exact_models, lex_order=False)
+                    if newly:
+                        s.status_t[torch.tensor(newly, device=s.status_t.device)] = SAT
+            self._update_pool(s, b, dec, leaf)
+        # partitions still running: no nodes left => UNSAT ; nodes left (time budget) => UNKNOWN.  The
+        # device status holds the budget / pool UNKNOWNs; the SATs confirmed on the host override it
+        v.status[:] = np.where(v.status == SAT, SAT, s.status_t.cpu().numpy())
+        v.nodes = s.nodes_t.cpu().numpy()
+        return v.sweep(s.pool.part.cpu().numpy()).result(t0, it)
+
+    def _each(self, fn, *sets) -> _Nodes:
+        """``fn`` over the columns of node sets; a PA-only query keeps x' an alias of x."""
+        lo, hi, plo, phi, part = zip(*sets)
+        lo, hi = fn(*lo), fn(*hi)
+        return _Nodes(lo, hi, fn(*plo) if self.relaxed else lo, fn(*phi) if self.relaxed else hi, fn(*part))
+
+    def _take_batch(self, s: _TorchSearch) -> Optional[_Nodes]:
+        """The pool's first ``batch_nodes`` nodes without those of decided partitions (None: none left)."""
+        B = min(self.cfg.batch_nodes, s.pool.part.shape[0])
+        b = self._each(lambda t: t[:B], s.pool)
+        s.pool = self._each(lambda t: t[B:], s.pool)
+        alive = s.status_t[b.part] == RUNNING
+        if not bool(alive.all()):
+            b = self._each(lambda t: t[alive], b)
+        if b.part.shape[0] == 0:
+            return None
+        s.nodes_t.index_add_(0, b.part, torch.ones_like(b.part))
+        return b
+
+    def _bound(self, s: _TorchSearch, b: _Nodes):
+        """Symbolic bounds of the batch's rows (one per PA assignment) and the pair certificate."""
+        cfg = self.cfg
+        dead_rows = None if self.dead is None else self.dead[b.part].repeat_interleave(s.values.shape[0], dim=0)
+        with self.tm("bab.bounds"):
+            rlo, rhi = self._rows(b.lo, b.hi, s.values)
+            rf = refine_on(cfg.refine, self.be.widths)
+            res_x = self.be.bounds(rlo, rhi, mode=cfg.mode, dead=dead_rows, crown=cfg.crown, refine=rf)
             if self.relaxed:
-                r = self.ra
-                cxp[:, r] = torch.minimum(torch.maximum(cxp[:, r], cx[:, r] - self.tau), cx[:, r] + self.tau)
-                cxp[:, r] = torch.minimum(torch.maximum(cxp[:, r], bplo[:, r]), bphi[:, r])
-            # ---- leaves: single lattice points (x and x'); evaluate every pair exactly
-            wmask = torch.ones(blo.shape[1], dtype=torch.bool, device=blo.device)
-            wmask[self.pa] = False
-            width = (bhi - blo)[:, wmask].amax(dim=1)
-            if self.relaxed:
-                width = torch.maximum(width, (bphi - bplo)[:, self.ra].amax(dim=1) if self.ra.numel() else width)
-            leaf = open_ & (width == 0)
-            sel = open_ & (status_t[bpart] == RUNNING)
-            cand_rows = torch.nonzero(sel & ~leaf).flatten()
-            found_idx: List[int] = []
-            found_x: List[np.ndarray] = []
-            found_xp: List[np.ndarray] = []
-            if cand_rows.numel():
-                with self.tm("bab.eval_cand"):
-                    sure, amb = self._eval_pairs(cx[cand_rows], cxp[cand_rows], bpart[cand_rows])
-                hit = cand_rows[sure | amb]
-                if hit.numel():
-                    found_idx.append(hit)
-            leaf_rows = torch.nonzero(leaf & sel).flatten()
-            if leaf_rows.numel():
-                # all pairs at the leaf point
-                L_ = leaf_rows.numel()
-                Pp = pairs.shape[0]
-                px = blo[leaf_rows][:, None, :].expand(L_, Pp, n).clone()
-                ppx = bplo[leaf_rows][:, None, :].expand(L_, Pp, n).clone()
-                px[:, :, self.pa] = values[pairs[:, 0]].to(px.dtype)[None].expand(L_, Pp, -1)
-                ppx[:, :, self.pa] = values[pairs[:, 1]].to(px.dtype)[None].expand(L_, Pp, -1)
-                lp = bpart[leaf_rows][:, None].expand(L_, Pp)
-                sure, amb = self._eval_pairs(px.reshape(-1, n), ppx.reshape(-1, n), lp.reshape(-1))
-                flag = (sure | amb).view(L_, Pp)
-                anyf = flag.any(dim=1)
-                if bool(anyf.any()):
-                    first = flag.float().argmax(dim=1)
-                    sel_l = torch.nonzero(anyf).flatten()
-                    found_idx.append(leaf_rows[sel_l])
-                    fx = px[sel_l, first[sel_l]]
-                    fxp = ppx[sel_l, first[sel_l]]
-                    cx[leaf_rows[sel_l]] = fx
-                    cxp[leaf_rows[sel_l]] = fxp
-            if found_idx:
-                rows = torch.cat(found_idx)
-                with self.tm("bab.confirm"):
-                    self._confirm(rows, cx, cxp, bpart, status, status_t, cex_x, cex_xp, mlp_exact, exact_models,
-                              lo_np, hi_np)
-            # ---- split open, non-leaf nodes of running partitions
-            nodes_np_now = nodes_t  # device
-            budget_ok = nodes_np_now[bpart] < cfg.node_budget
-            split = open_ & ~leaf & (status_t[bpart] == RUNNING) & budget_ok
-            # partitions that ran out of budget with open nodes -> UNKNOWN
-            over = open_ & ~leaf & (status_t[bpart] == RUNNING) & ~budget_ok
-            if bool(over.any()):
-                status_t[bpart[over]] = UNKNOWN
-            sidx = torch.nonzero(split).flatten()
-            with self.tm("bab.split"):
-                new = self._split(blo[sidx], bhi[sidx], bplo[sidx], bphi[sidx], bpart[sidx], dec.split_dim[sidx])
-            # ---- next pool = rest + children
-            if self.relaxed:
-                clo, chi, cplo, cphi, cpart = new
-                xlo = torch.cat([xlo[rest], clo])
-                xhi = torch.cat([xhi[rest], chi])
-                xplo = torch.cat([xplo[rest], cplo])
-                xphi = torch.cat([xphi[rest], cphi])
-                part = torch.cat([part[rest], cpart])
+                plo, phi = self._rows(b.plo, b.phi, s.values)
+                res_xp = self.be.bounds(plo, phi, mode=cfg.mode, dead=dead_rows, crown=cfg.crown, refine=rf)
             else:
-                clo, chi, _, _, cpart = new
-                xlo = torch.cat([xlo[rest], clo])
-                xhi = torch.cat([xhi[rest], chi])
-                xplo, xphi = xlo, xhi
-                part = torch.cat([part[rest], cpart])
-            if xlo.shape[0] > cfg.max_pool:
-                # keep the oldest nodes; partitions losing nodes become UNKNOWN
-                lost = torch.unique(part[cfg.max_pool:])
-                status_t[lost[status_t[lost] == RUNNING]] = UNKNOWN
-                xlo, xhi, part = xlo[:cfg.max_pool], xhi[:cfg.max_pool], part[:cfg.max_pool]
-                if self.relaxed:
-                    xplo, xphi = xplo[:cfg.max_pool], xphi[:cfg.max_pool]
-                else:
-                    xplo, xphi = xlo, xhi
-        # partitions still running: no nodes left => UNSAT ; nodes left (time budget) => UNKNOWN
-        st = status_t.cpu().numpy()
-        remaining = set(part.cpu().numpy().tolist()) if xlo.shape[0] else set()
-        for p in np.nonzero(st == RUNNING)[0]:
-            st[p] = UNKNOWN if p in remaining else UNSAT
-        # SAT found on host overrides
-        st[status == SAT] = SAT
-        nodes_np = nodes_t.cpu().numpy()
-        return BaBResult(st.astype(np.int8), cex_x, cex_xp, nodes_np, it, time.time() - t0)
+                res_xp = res_x
+        with self.tm("bab.certify"):
+            return self.be.pair_certify(res_x, res_xp, b.lo, b.hi, b.plo, b.phi, s.pairs, s.values, self.pa,
+                                        self.shared, self.relaxed)
+
+    def _candidates(self, s: _TorchSearch, b: _Nodes, dec):
+        """Candidate vertex pairs (falsification inside BaB): the pairs, the leaf mask, the open nodes of
+        running partitions, and (a list) the rows whose pair the rigorous evaluation cannot rule out."""
+        values, pv = s.values, s.pairs[dec.cand_v]
+        cx, cxp = dec.cand_x.clone(), dec.cand_xp.clone()
+        cx[:, self.pa] = values[pv[:, 0]].to(cx.dtype)
+        cxp[:, self.pa] = values[pv[:, 1]].to(cx.dtype)
+        if self.relaxed:
+            r = self.ra
+            cxp[:, r] = clamp_tau(cxp[:, r], cx[:, r], self.tau)
+            cxp[:, r] = torch.minimum(torch.maximum(cxp[:, r], b.plo[:, r]), b.phi[:, r])
+        # leaves: single lattice points (x and x')
+        wmask = torch.ones(b.lo.shape[1], dtype=torch.bool, device=b.lo.device)
+        wmask[self.pa] = False
+        width = (b.hi - b.lo)[:, wmask].amax(dim=1)
+        if self.relaxed:
+            width = torch.maximum(width, (b.phi - b.plo)[:, self.ra].amax(dim=1) if self.ra.numel() else width)
+        leaf = dec.open_ & (width == 0)
+        sel = dec.open_ & (s.status_t[b.part] == RUNNING)
+        cand_rows = torch.nonzero(sel & ~leaf).flatten()
+        found = []
+        if cand_rows.numel():
+            with self.tm("bab.eval_cand"):
+                sure, amb = self._eval_pairs(cx[cand_rows], cxp[cand_rows], b.part[cand_rows])
+            hit = cand_rows[sure | amb]
+            if hit.numel():
+                found.append(hit)
+        return cx, cxp, leaf, sel, found
+
+    def _leaves(self, s: _TorchSearch, b: _Nodes, leaf_rows: torch.Tensor, cx, cxp) -> list:
+        """All PA pairs at the leaf points: the leaves with a possible violation (its pair put into cx / cxp)."""
+        if not leaf_rows.numel():
+            return []
+        values, pairs, n = s.values, s.pairs, b.lo.shape[1]
+        L_, Pp = leaf_rows.numel(), pairs.shape[0]
+        px = b.lo[leaf_rows][:, None, :].expand(L_, Pp, n).clone()
+        ppx = b.plo[leaf_rows][:, None, :].expand(L_, Pp, n).clone()
+        px[:, :, self.pa] = values[pairs[:, 0]].to(px.dtype)[None].expand(L_, Pp, -1)
+        ppx[:, :, self.pa] = values[pairs[:, 1]].to(px.dtype)[None].expand(L_, Pp, -1)
+        lp = b.part[leaf_rows][:, None].expand(L_, Pp)
+        sure, amb = self._eval_pairs(px.reshape(-1, n), ppx.reshape(-1, n), lp.reshape(-1))
+        flag = (sure | amb).view(L_, Pp)
+        anyf = flag.any(dim=1)
+        if not bool(anyf.any()):
+            return []
+        first = flag.float().argmax(dim=1)
+        sel_l = torch.nonzero(anyf).flatten()
+        cx[leaf_rows[sel_l]] = px[sel_l, first[sel_l]]
+        cxp[leaf_rows[sel_l]] = ppx[sel_l, first[sel_l]]
+        return [leaf_rows[sel_l]]
+
+    def _update_pool(self, s: _TorchSearch, b: _Nodes, dec, leaf: torch.Tensor) -> None:
+        """Open non-leaf nodes of running partitions split while the partition is within its node budget
+        (the device-side count), else it ends UNKNOWN; next pool = rest + children, cut to ``max_pool``."""
+        cfg = self.cfg
+        grow = dec.open_ & ~leaf & (s.status_t[b.part] == RUNNING)
+        budget_ok = s.nodes_t[b.part] < cfg.node_budget
+        over = grow & ~budget_ok
+        if bool(over.any()):
+            s.status_t[b.part[over]] = UNKNOWN
+        sidx = torch.nonzero(grow & budget_ok).flatten()
+        with self.tm("bab.split"):
+            kids = self._split(*(t[sidx] for t in b), dec.split_dim[sidx])
+        s.pool = self._each(lambda rest, new: torch.cat([rest, new]), s.pool, kids)
+        if s.pool.part.shape[0] > cfg.max_pool:     # keep the oldest nodes; partitions losing nodes become UNKNOWN
+            pool_overflow(s.pool.part, cfg.max_pool, s.status_t)
+            s.pool = self._each(lambda t: t[:cfg.max_pool], s.pool)
 
     def _solve_groups(self, groups, lo_np, hi_np, mlp_exact, init_status, exact_models, t0) -> BaBResult:
-        """Partitions with different protected-attribute ranges: one solve per PA group (each has
-        its own table of PA assignments), results scattered back in input order.  Per-partition
-        forced-dead masks and masked exact models follow their partitions into the group."""
-        P, n = lo_np.shape
-        status = np.full(P, RUNNING, dtype=np.int8) if init_status is None else init_status.astype(np.int8).copy()
-        cex_x = np.zeros((P, n), dtype=np.int64)
-        cex_xp = np.zeros((P, n), dtype=np.int64)
-        nodes = np.zeros(P, dtype=np.int64)
-        open_left = np.zeros(P, dtype=np.int64)
-        iters = 0
-        dead_all = self.dead
-        for g in groups:
-            sub = BaBSolver(self.be, self.q, replace(self.cfg, time_budget=max(0.0, self.cfg.time_budget -
-                                                                                  (time.time() - t0))),
-                            dead=None if dead_all is None else dead_all[torch.from_numpy(g).to(dead_all.device)],
+        """Partitions with different PA ranges: a sub-solver per PA group, with the group's rows of the
+        forced-dead masks and its masked exact models; ``open_left`` zeros where a group reports none."""
+        def one(g, status_g, left):
+            sub = BaBSolver(self.be, self.q, replace(self.cfg, time_budget=left),
+                            dead=None if self.dead is None else self.dead[torch.from_numpy(g).to(self.dead.device)],
                             timer=self.tm)
             em = None if exact_models is None else [exact_models[int(k)] for k in g]
-            r = sub.solve(lo_np[g], hi_np[g], mlp_exact, init_status=status[g], exact_models=em)
-            status[g], cex_x[g], cex_xp[g], nodes[g] = r.status, r.cex_x, r.cex_xp, r.nodes
-            if r.open_left is not None:
-                open_left[g] = r.open_left
-            iters += r.iters
-        return BaBResult(status, cex_x, cex_xp, nodes, iters, time.time() - t0, open_left=open_left)
+            return sub.solve(lo_np[g], hi_np[g], mlp_exact, init_status=status_g, exact_models=em)
+
+        return solve_pa_groups(groups, lo_np, hi_np, init_status, self.cfg.time_budget, t0, one, open_left=True)
 
     # --------------------------------------------------------------------------------------
     def _runtime(self, values_np: np.ndarray, pairs_np: np.ndarray, n_run: int):
@@ -440,67 +384,24 @@ class BaBSolver:
         return BaBResult(np.asarray(st, dtype=np.int8), np.asarray(cx), np.asarray(cxp), np.asarray(nodes),
                          int(stats["levels"]), time.time() - t0, open_left=np.asarray(stats["open_left"]))
 
-    # --------------------------------------------------------------------------------------
-    def _confirm(self, rows, cx, cxp, bpart, status, status_t, cex_x, cex_xp, mlp_exact, exact_models,
-                 lo_np, hi_np):
-        r = rows.cpu().numpy()
-        X = cx[rows].cpu().numpy().round().astype(np.int64)
-        XP = cxp[rows].cpu().numpy().round().astype(np.int64)
-        parts = bpart[rows].cpu().numpy()
-        ok = exact.check_pair_constraints(X, XP, lo_np[parts], hi_np[parts], self.q.pa_idx, self.q.ra_idx,
-                                          self.q.tau)
-        if exact_models is None:
-            viol = exact.is_violation(mlp_exact, X, XP) & ok
-        else:
-            viol = np.zeros(len(parts), dtype=bool)
-            for k, p in enumerate(parts):
-                if ok[k]:
-                    viol[k] = exact.is_violation(exact_models[p], X[k:k + 1], XP[k:k + 1])[0]
-        newly = []
-        for k in np.nonzero(viol)[0]:
-            p = parts[k]
-            if status[p] != SAT:
-                status[p] = SAT
-                cex_x[p] = X[k]
-                cex_xp[p] = XP[k]
-                newly.append(p)
-        if newly:
-            status_t[torch.tensor(newly, device=status_t.device)] = SAT
-
     def _split(self, lo, hi, plo, phi, part, dim):
         n = lo.shape[1]
-        N = lo.shape[0]
-        if N == 0:
-            e = lo[:0]
-            return e, e, e, e, part[:0]
+        if lo.shape[0] == 0:
+            return lo[:0], lo[:0], lo[:0], lo[:0], part[:0]
+        # children along x dim or x' dim
         on_x = dim < n
         d = torch.where(on_x, dim, dim - n)
-        ar = torch.arange(N, device=lo.device)
-        # children along x dim or x' dim
-        src_lo = torch.where(on_x, lo[ar, d], plo[ar, d])
-        src_hi = torch.where(on_x, hi[ar, d], phi[ar, d])
-        mid = torch.floor((src_lo + src_hi) / 2)
-        lo1, hi1, lo2, hi2 = lo.clone(), hi.clone(), lo.clone(), hi.clone()
-        plo1, phi1, plo2, phi2 = plo.clone(), phi.clone(), plo.clone(), phi.clone()
-        xs = torch.nonzero(on_x).flatten()
-        ps = torch.nonzero(~on_x).flatten()
-        hi1[xs, d[xs]] = mid[xs]
-        lo2[xs, d[xs]] = mid[xs] + 1
-        phi1[ps, d[ps]] = mid[ps]
-        plo2[ps, d[ps]] = mid[ps] + 1
-        clo = torch.cat([lo1, lo2])
-        chi = torch.cat([hi1, hi2])
-        cplo = torch.cat([plo1, plo2])
-        cphi = torch.cat([phi1, phi2])
-        cpart = torch.cat([part, part])
+        xs, ps = torch.nonzero(on_x).flatten(), torch.nonzero(~on_x).flatten()
+        lo1, hi1, lo2, hi2 = halve(lo, hi, xs, d[xs])
+        plo1, phi1, plo2, phi2 = halve(plo, phi, ps, d[ps])
+        clo, chi, cpart = torch.cat([lo1, lo2]), torch.cat([hi1, hi2]), torch.cat([part, part])
+        cplo, cphi = torch.cat([plo1, plo2]), torch.cat([phi1, phi2])
         if not self.relaxed:
             return clo, chi, clo, chi, cpart
         # shared dims of x' follow x; tighten the |x_r - x'_r| <= tau coupling
-        sh = self.shared
-        cplo = torch.where(sh[None, :], clo, cplo)
-        cphi = torch.where(sh[None, :], chi, cphi)
-        r = self.ra
-        t = self.tau
+        cplo = torch.where(self.shared[None, :], clo, cplo)
+        cphi = torch.where(self.shared[None, :], chi, cphi)
+        r, t = self.ra, self.tau
         cplo[:, r] = torch.maximum(cplo[:, r], clo[:, r] - t)
         cphi[:, r] = torch.minimum(cphi[:, r], chi[:, r] + t)
         clo[:, r] = torch.maximum(clo[:, r], cplo[:, r] - t)

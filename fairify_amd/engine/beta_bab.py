@@ -20,7 +20,8 @@ Relaxed queries (|x_r - x'_r| <= tau, x' unclipped): every node also carries x''
 dims, split like the input dims, and its orientation: N(x, va) < 0 < N(x', vb) or the reverse (x' may
 leave the box, so the swapped pair does not cover the second one); both orientations are roots of the
 same search (the objective's sign per node).  CPU tests pin verdicts to brute-force enumeration
-(tests/test_beta_bab.py); the GPU kernel to this module's reference (tests/test_beta_gpu.py).
+(tests/test_beta_bab.py); the GPU kernel to this module's reference (tests/test_beta_gpu.py).  ``_roots`` builds
+the roots for both the native runtime and the torch loop (``_torch_level``); the host layer is engine/search.py.
 """
 from __future__ import annotations
 
@@ -28,6 +29,7 @@ import os
 import sys
 import time
 from dataclasses import dataclass, replace
+from types import SimpleNamespace
 from typing import Optional
 
 import numpy as np
@@ -39,7 +41,9 @@ from ..ops.backend import Backend
 from ..spec import ResolvedQuery
 from ..utils.timer import NULL, StageTimer
 from . import exact
-from .bab import RUNNING, SAT, UNKNOWN, UNSAT, BaBResult, _pa_table, pa_groups
+from .relu_bab import negated
+from .search import (RUNNING, UNKNOWN, UNSAT, BaBResult, Verdicts, clamp_tau, confirm_pairs, merge_orientations,
+                     pa_groups, pa_table, pool_overflow, solve_pa_groups, tau_apart)
 
 
 @dataclass
@@ -124,9 +128,7 @@ def fits(be: Backend) -> bool:
 
 class BetaBaBSolver:
     def __init__(self, backend: Backend, query: ResolvedQuery, cfg: BetaConfig, timer: StageTimer = NULL):
-        self.be = backend
-        self.q = query
-        self.cfg = cfg
+        self.be, self.q, self.cfg = backend, query, cfg
         # the kernels' flags word holds the weights in two bits (ops/hip.py:beta_flags): a larger value
         # would read as the infeasibility pass's bit
         if not 0 <= int(cfg.pgap_weights) <= 3:
@@ -142,48 +144,27 @@ class BetaBaBSolver:
         negated (x' may leave the box, so swapping the pair does not cover it); UNSAT when both
         close, SAT when either finds a pair (confirmed on ``mlp_exact``, orientation-free)."""
         t0 = time.time()
-        P, n = lo_np.shape
-        status = np.full(P, RUNNING, dtype=np.int8) if init_status is None else init_status.astype(np.int8).copy()
-        cex_x = np.zeros((P, n), dtype=np.int64)
-        cex_xp = np.zeros((P, n), dtype=np.int64)
-        nodes = np.zeros(P, dtype=np.int64)
+        v = Verdicts(*lo_np.shape, init_status)
         if not supported(self.q) or self.be.n_hidden == 0 or not fits(self.be):
-            status[status == RUNNING] = UNKNOWN
-            return BaBResult(status, cex_x, cex_xp, nodes)
+            return v.close_running(UNKNOWN).result()     # before either orientation is solved
         self.stats = {"levels": 0, "nodes": 0}
-        r1 = self._solve_all(lo_np, hi_np, mlp_exact, status, t0)
+        r1 = solve_pa_groups(pa_groups(self.q, lo_np, hi_np), lo_np, hi_np, v.status, self.cfg.time_budget, t0,
+                             lambda g, st, left: self._solve_group(lo_np[g], hi_np[g], mlp_exact, st, left))
         if not self.q.relaxed or getattr(self, "_second", False) or self.cfg.merge_orient:
             return r1
-        closed = (r1.status == UNSAT) & (status == RUNNING)
-        if not closed.any():
-            return r1
-        from .relu_bab import negated
 
-        neg = BetaBaBSolver(Backend(negated(self.be.mlp), device=self.dev), self.q,
-                            replace(self.cfg, time_budget=max(0.0, self.cfg.time_budget - (time.time() - t0))),
-                            timer=self.tm)
-        neg._second = True
-        r2 = neg.solve(lo_np, hi_np, mlp_exact, init_status=np.where(closed, RUNNING, UNKNOWN).astype(np.int8))
-        out = r1.status.copy()
-        out[closed] = r2.status[closed]
-        cx, cxp = r1.cex_x.copy(), r1.cex_xp.copy()
-        s2 = closed & (r2.status == SAT)
-        cx[s2], cxp[s2] = r2.cex_x[s2], r2.cex_xp[s2]
-        self.stats["nodes"] += neg.stats.get("nodes", 0)
-        self.stats["levels"] += neg.stats.get("levels", 0)
-        return BaBResult(out, cx, cxp, r1.nodes + r2.nodes, 0, time.time() - t0)
+        def second(st2):
+            # this config with the time left; the second solver's nodes and levels count as this one's
+            neg = BetaBaBSolver(Backend(negated(self.be.mlp), device=self.dev), self.q,
+                                replace(self.cfg, time_budget=max(0.0, self.cfg.time_budget - (time.time() - t0))),
+                                timer=self.tm)
+            neg._second = True
+            r2 = neg.solve(lo_np, hi_np, mlp_exact, init_status=st2)
+            self.stats["nodes"] += neg.stats.get("nodes", 0)
+            self.stats["levels"] += neg.stats.get("levels", 0)
+            return r2
 
-    def _solve_all(self, lo_np, hi_np, mlp_exact, status, t0) -> BaBResult:
-        P, n = lo_np.shape
-        status = status.copy()
-        cex_x = np.zeros((P, n), dtype=np.int64)
-        cex_xp = np.zeros((P, n), dtype=np.int64)
-        nodes = np.zeros(P, dtype=np.int64)
-        for g in pa_groups(self.q, lo_np, hi_np):
-            left = max(0.0, self.cfg.time_budget - (time.time() - t0))
-            st, cx, cxp, nd = self._solve_group(lo_np[g], hi_np[g], mlp_exact, status[g], left)
-            status[g], cex_x[g], cex_xp[g], nodes[g] = st, cx, cxp, nd
-        return BaBResult(status, cex_x, cex_xp, nodes, 0, time.time() - t0)
+        return merge_orientations(r1, v.status, second, t0)
 
     # ------------------------------------------------------------------------------------------
     def _root_bounds(self, lo: torch.Tensor, hi: torch.Tensor, values: torch.Tensor, widen: bool = False):
@@ -211,28 +192,50 @@ class BetaBaBSolver:
         self._logit = (res.out_lb, res.out_ub)          # [P * V] rigorous logit bounds of the rows
         return lb, ub
 
-    def _solve_group(self, lo_np, hi_np, mlp_exact, status, time_budget):
+    def _solve_group(self, lo_np, hi_np, mlp_exact, status, time_budget) -> BaBResult:
         t0 = time.time()
-        be, q, cfg = self.be, self.q, self.cfg
-        dev = self.dev
-        P, n0 = lo_np.shape
-        NH = be.n_hidden
-        status = status.copy()
-        cex_x = np.zeros((P, n0), dtype=np.int64)
-        cex_xp = np.zeros((P, n0), dtype=np.int64)
-        nodes_np = np.zeros(P, dtype=np.int64)
-        values_np, pairs_np = _pa_table(q, lo_np, hi_np)
-        run = np.nonzero(status == RUNNING)[0]
-        Pp = pairs_np.shape[0]
+        v = Verdicts(*lo_np.shape, status)
+        s = self._roots(lo_np, hi_np, mlp_exact, v)
+        if s is None:
+            return v.result()
+        if self._use_native(s.O):
+            return self._solve_native(s, max(0.0, time_budget - (time.time() - t0)))
+        levels, timed_out = 0, False         # the torch loop; stats accumulate over the groups of a call
+        while s.pool["part"].numel():
+            if time.time() - t0 > time_budget:
+                timed_out = True
+                break
+            # drop nodes of decided / over-budget partitions, and (relaxed) nodes whose x and x'
+            # RA boxes are more than tau apart (no admissible pair left)
+            pool, ra = s.pool, s.ra
+            alive = torch.from_numpy(v.status == RUNNING).to(self.dev)[pool["part"]]
+            if s.relaxed:
+                alive &= ~tau_apart(pool["lo"][:, ra], pool["hi"][:, ra], pool["plo"][:, ra], pool["phi"][:, ra], s.tau)
+            if not bool(alive.all()):
+                s.pool = {kk: t[alive] for kk, t in pool.items()}
+                if not s.pool["part"].numel():
+                    break
+            levels += 1
+            self._torch_level(s)
+        v.sweep(s.pool["part"].cpu().numpy() if timed_out else ())
+        self.stats["levels"] = self.stats.get("levels", 0) + levels
+        self.stats["nodes"] = self.stats.get("nodes", 0) + int(v.nodes.sum())
+        return v.result()
+
+    def _roots(self, lo_np, hi_np, mlp_exact, v: Verdicts) -> Optional[SimpleNamespace]:
+        """Root construction of one PA group, for the native and the torch path: PA table, root bounds, sign
+        prune, the ``pool`` (a root per running partition, ordered pair, orientation), ``tree_run`` /
+        ``pre_closed`` for the probe, ``budget``.  None: the group is decided without a search (in ``v``)."""
+        be, q, cfg, dev = self.be, self.q, self.cfg, self.dev
+        (P, n0), NH = lo_np.shape, be.n_hidden
+        values_np, pairs_np = pa_table(q, lo_np, hi_np)
+        run, Pp = np.nonzero(v.status == RUNNING)[0], pairs_np.shape[0]
         if Pp == 0:
-            status[run] = UNSAT
-            return status, cex_x, cex_xp, nodes_np
-        if run.size == 0:
-            return status, cex_x, cex_xp, nodes_np
-        pa = list(q.pa_idx)
-        relaxed = q.relaxed
+            v.close_running(UNSAT)
+        if Pp == 0 or run.size == 0:
+            return None
+        relaxed, tau = q.relaxed, float(q.tau)
         ra = list(q.ra_idx) if relaxed else []
-        tau = float(q.tau)
         ram = torch.zeros(n0, dtype=torch.bool, device=dev)
         ram[ra] = True
         f32 = dict(dtype=torch.float32, device=dev)
@@ -252,9 +255,8 @@ class BetaBaBSolver:
         pr = torch.from_numpy(pairs_np.astype(np.int64)).to(dev).repeat_interleave(O, dim=0).repeat(run.size, 1)
         osg = torch.tensor([1, -1][:O], dtype=torch.int8, device=dev).repeat(run.size * Pp)
         ia, ib = k * V + pr[:, 0], k * V + pr[:, 1]
-        self.stats["native"] = self._use_native(O)       # the loop this group runs on (tests / logs)
-        self.stats["batched"] = self._batched()
-        self.stats["batched_feas"] = self._batched_feas()
+        # the loop this group runs on (tests / logs)
+        self.stats.update(native=self._use_native(O), batched=self._batched(), batched_feas=self._batched_feas())
         if cfg.trees:        # experiment: one tree at a time (tools/exp/beta_vs_lp.py)
             jj = torch.arange(Pp, device=dev).repeat_interleave(O).repeat(run.size)
             sel = torch.zeros_like(k, dtype=torch.bool)
@@ -276,11 +278,9 @@ class BetaBaBSolver:
             k, pr, osg, ia, ib = k[keep], pr[keep], osg[keep], ia[keep], ib[keep]
             self.stats["sign_pruned"] = self.stats.get("sign_pruned", 0) + int(dead.sum())
             if k.numel() == 0:
-                status[run] = UNSAT
-                return status, cex_x, cex_xp, nodes_np
-        R0 = k.numel()
-        plo = lo_r[k].clone()
-        phi = hi_r[k].clone()
+                v.status[run] = UNSAT
+                return None
+        R0, plo, phi = k.numel(), lo_r[k].clone(), hi_r[k].clone()
         if relaxed:                 # x' on the RA dims: [lo - tau, hi + tau], unclipped
             plo[:, ra] -= tau
             phi[:, ra] += tau
@@ -301,126 +301,112 @@ class BetaBaBSolver:
             "tree": torch.arange(R0, device=dev),        # the (partition, ordered pair, orientation) root
             "osg": osg,
         }
-        tree_run = run[k.cpu().numpy()]
-        # node budget per partition, scaled with its ordered pairs (a multi-valued PA -- race: 20
-        # pairs -- gets the budget a binary one gets per pair)
-        budget = int(cfg.node_budget * max(1.0, Pp / 2.0) * O)
-        if self._use_native(O):
-            return self._solve_native(pool, R0, status, lo_np, hi_np, mlp_exact, budget,
-                                      2 * cfg.probe_levels * Pp * O if cfg.probe_levels else 0,
-                                      max(0.0, time_budget - (time.time() - t0)), pre_closed)
-        levels = 0
-        # the probe (per partition, so a verdict never depends on which partitions share the call):
-        # once a partition has expanded 2 probe_levels nodes per pair tree, it goes on only if one
-        # of its trees has closed
-        probed = np.zeros(P, dtype=bool)
-        probe_at = 2 * cfg.probe_levels * Pp * O
-        timed_out = False
-        while pool["part"].numel():
-            if time.time() - t0 > time_budget:
-                timed_out = True
-                break
-            # drop nodes of decided / over-budget partitions, and (relaxed) nodes whose x and x'
-            # RA boxes are more than tau apart (no admissible pair left)
-            alive = torch.from_numpy(status == RUNNING).to(dev)[pool["part"]]
-            if relaxed:
-                alive &= ~((pool["plo"][:, ra] > pool["hi"][:, ra] + tau) |
-                           (pool["phi"][:, ra] < pool["lo"][:, ra] - tau)).any(1)
-            if not bool(alive.all()):
-                pool = {kk: v[alive] for kk, v in pool.items()}
-                if not pool["part"].numel():
-                    break
-            # the front batch: roots first (their own iteration count), then FIFO
-            nb = min(cfg.batch_nodes, pool["part"].numel())
-            is_root = bool(pool["root"][0])
-            if is_root:
-                nb = min(nb, int(pool["root"].sum()))
-            cur = {kk: v[:nb] for kk, v in pool.items()}
-            rest = {kk: v[nb:] for kk, v in pool.items()}
-            levels += 1
-            np.add.at(nodes_np, cur["part"].cpu().numpy(), 1)
-            sc = 1.0 if is_root else cfg.child_lr
-            empty = None
-            if cfg.tighten and not is_root:
-                with self.tm("beta.tighten"):
-                    empty = self._tighten(cur, pa, ram if relaxed else None)
-            rx = (ram, cur["plo"], cur["phi"], tau, cur["gP"], cur["gM"]) if relaxed else None
-            with self.tm("beta.level"):
-                lev = be.beta_level(cur["lo"], cur["hi"], pa, cur["va"], cur["vb"], cur["LBA"], cur["UBA"],
-                                    cur["LBB"], cur["UBB"], cur["phA"], cur["phB"], cur["alA"], cur["alB"],
-                                    cur["beA"], cur["beB"], cur["t"], cfg.root_iters if is_root else cfg.iters,
-                                    cfg.lr_a * sc, cfg.lr_b * sc, cfg.lr_t * sc, cfg.decay, cfg.lookahead,
-                                    cfg.beta_pos, rx, pgap=cfg.pgap_weights if cfg.branch == "pgap" else 0,
-                                    osg=cur["osg"] if O > 1 else None,
-                                    feas_iters=0 if is_root else cfg.feas_iters,
-                                    feas_lr=(cfg.lr_a, cfg.lr_b, cfg.lr_t), batched=self._batched(),
-                                    batched_feas=self._batched_feas())
-            if empty is not None:
-                lev.bound = torch.where(empty, torch.full_like(lev.bound, float("inf")), lev.bound)
-            closed = lev.bound >= 0
-            nan = torch.isnan(lev.bound)
-            if bool(nan.any()):
-                # a node without a bound cannot close its tree: its partition stops (UNKNOWN), as in the
-                # native loop (csrc/beta_bab.hip split kernel)
-                bad = np.unique(cur["part"][nan].cpu().numpy())
-                self.stats["nan_nodes"] = self.stats.get("nan_nodes", 0) + int(nan.sum())
-                status[bad[status[bad] == RUNNING]] = UNKNOWN
-            leaf = lev.split == B.LEAF(n0)
-            # candidate vertex pairs of the nodes that stay open (and the lattice leaves): rigorous
-            # point bounds screen, then the exact check on the host
-            cand = torch.nonzero(~closed).flatten()
-            if cand.numel():
-                xa = lev.xstar[cand].clone()
-                xb = (lev.xpstar[cand] if lev.xpstar is not None else lev.xstar[cand]).clone()
-                if relaxed:         # x'_r: its vertex, pulled into [x_r - tau, x_r + tau]
-                    xb[:, ra] = torch.minimum(torch.maximum(xb[:, ra], xa[:, ra] - tau), xa[:, ra] + tau)
-                xa[:, pa] = cur["va"][cand]
-                xb[:, pa] = cur["vb"][cand]
-                with self.tm("beta.cand"):
-                    alb, aub = be.point_bounds(xa)
-                    blb, bub = be.point_bounds(xb)
-                poss = (alb < 0) & (bub > 0)
-                if O > 1:       # orientation -1: N(x, va) > 0 > N(x', vb)
-                    poss = torch.where(cur["osg"][cand] > 0, poss, (aub > 0) & (blb < 0))
-                ci = cand[poss]
-                if ci.numel():
-                    self._confirm(cur["part"][ci].cpu().numpy(), xa[poss], xb[poss], status, cex_x, cex_xp,
-                                  mlp_exact, lo_np, hi_np)
-            grow = ~closed & ~leaf
-            run_t = torch.from_numpy(status == RUNNING).to(dev)[cur["part"]]
-            grow &= run_t
-            over = torch.from_numpy(nodes_np >= budget).to(dev)[cur["part"]] & grow
-            if bool(over.any()):
-                ob = np.unique(cur["part"][over].cpu().numpy())
-                self.stats["over_budget"] = self.stats.get("over_budget", 0) + int((status[ob] == RUNNING).sum())
-                status[ob] = UNKNOWN
-                grow &= ~over
-            gi = torch.nonzero(grow).flatten()
-            bi = lev.binit[gi] if cfg.warm_beta else torch.zeros_like(lev.binit[gi])
-            split = lev.split[gi]
-            if cfg.branch == "lpgap" and gi.numel():
-                ns = self._lp_gap_split(cur, gi, lev, pa, ra, tau, NH)
-                moved = (split >= 0) & (ns >= 0) & (ns != split)
-                split = torch.where(moved, ns, split)
-                bi = torch.where(moved[:, None], torch.zeros_like(bi), bi)   # new neuron: beta from 0
-            if cfg.input_every > 0 and gi.numel():
-                split = self._force_input(cur, gi, split, pa, ra, n0, cfg.input_every)
-            kids = self._children({kk: v[gi] for kk, v in cur.items()}, split, bi, NH, n0)
-            pool = {kk: torch.cat([rest[kk], kids[kk]]) for kk in pool}
-            if cfg.probe_levels:
-                self._probe(pool, nodes_np, probed, probe_at, R0, tree_run, status, pre_closed)
-            if pool["part"].numel() > cfg.max_pool:
-                lost = torch.unique(pool["part"][cfg.max_pool:]).cpu().numpy()
-                lost = lost[status[lost] == RUNNING]
-                self.stats["pool_lost"] = self.stats.get("pool_lost", 0) + int(lost.size)
-                status[lost] = UNKNOWN
-                pool = {kk: v[:cfg.max_pool] for kk, v in pool.items()}
-        left = set(pool["part"].cpu().numpy().tolist()) if (timed_out and pool["part"].numel()) else set()
-        for p in np.nonzero(status == RUNNING)[0]:
-            status[p] = UNKNOWN if p in left else UNSAT
-        self.stats["levels"] = self.stats.get("levels", 0) + levels
-        self.stats["nodes"] = self.stats.get("nodes", 0) + int(nodes_np.sum())
-        return status, cex_x, cex_xp, nodes_np
+        # node budget per partition, scaled with its ordered pairs (a multi-valued PA -- race: 20 pairs -- gets
+        # the budget a binary one gets per pair) and orientations.  The probe (per partition: no verdict depends on
+        # which partitions share the call): past 2 probe_levels nodes per pair tree, only if a tree has closed
+        return SimpleNamespace(v=v, lo_np=lo_np, hi_np=hi_np, mlp_exact=mlp_exact, pool=pool, R0=R0, O=O, NH=NH,
+                               pa=list(q.pa_idx), relaxed=relaxed, ra=ra, tau=tau, ram=ram,
+                               tree_run=run[k.cpu().numpy()], pre_closed=pre_closed,
+                               budget=int(cfg.node_budget * max(1.0, Pp / 2.0) * O),
+                               probe_at=2 * cfg.probe_levels * Pp * O, probed=np.zeros(P, dtype=bool))
+
+    def _level(self, s: SimpleNamespace, nd, is_root: bool, osg, **kw):
+        """The bound kernel's call on the nodes ``nd`` (their parameters are updated in place)."""
+        cfg = self.cfg
+        sc = 1.0 if is_root else cfg.child_lr
+        rx = (s.ram, nd["plo"], nd["phi"], s.tau, nd["gP"], nd["gM"]) if s.relaxed else None
+        return self.be.beta_level(nd["lo"], nd["hi"], s.pa, nd["va"], nd["vb"], nd["LBA"], nd["UBA"], nd["LBB"],
+                                  nd["UBB"], nd["phA"], nd["phB"], nd["alA"], nd["alB"], nd["beA"], nd["beB"], nd["t"],
+                                  cfg.root_iters if is_root else cfg.iters, cfg.lr_a * sc, cfg.lr_b * sc,
+                                  cfg.lr_t * sc, cfg.decay, cfg.lookahead, cfg.beta_pos, rx,
+                                  pgap=cfg.pgap_weights if cfg.branch == "pgap" else 0, osg=osg, **kw)
+
+    def _torch_level(self, s: SimpleNamespace) -> None:
+        """One level on the pool's front batch: roots first (their own iteration count), then FIFO."""
+        cfg, pool, v = self.cfg, s.pool, s.v
+        nb = min(cfg.batch_nodes, pool["part"].numel())
+        is_root = bool(pool["root"][0])
+        if is_root:
+            nb = min(nb, int(pool["root"].sum()))
+        cur, rest = {kk: t[:nb] for kk, t in pool.items()}, {kk: t[nb:] for kk, t in pool.items()}
+        np.add.at(v.nodes, cur["part"].cpu().numpy(), 1)
+        lev, closed = self._bound(s, cur, is_root)
+        self._candidates(s, cur, lev, torch.nonzero(~closed).flatten())
+        kids = self._branch(s, cur, lev, closed)
+        pool = {kk: torch.cat([rest[kk], kids[kk]]) for kk in pool}
+        if cfg.probe_levels:
+            self._probe(pool, v.nodes, s.probed, s.probe_at, s.R0, s.tree_run, v.status, s.pre_closed)
+        if pool["part"].numel() > cfg.max_pool:
+            lost = pool_overflow(pool["part"], cfg.max_pool, v.status)
+            self.stats["pool_lost"] = self.stats.get("pool_lost", 0) + lost
+            pool = {kk: t[:cfg.max_pool] for kk, t in pool.items()}
+        s.pool = pool
+
+    def _bound(self, s: SimpleNamespace, cur, is_root: bool):
+        """The batch's bounds (children: after tightening their hidden bounds): level record, closed nodes."""
+        cfg = self.cfg
+        empty = None
+        if cfg.tighten and not is_root:
+            with self.tm("beta.tighten"):
+                empty = self._tighten(cur, s.pa, s.ram if s.relaxed else None)
+        with self.tm("beta.level"):
+            lev = self._level(s, cur, is_root, cur["osg"] if s.O > 1 else None,
+                              feas_iters=0 if is_root else cfg.feas_iters, feas_lr=(cfg.lr_a, cfg.lr_b, cfg.lr_t),
+                              batched=self._batched(), batched_feas=self._batched_feas())
+        if empty is not None:
+            lev.bound = torch.where(empty, torch.full_like(lev.bound, float("inf")), lev.bound)
+        nan = torch.isnan(lev.bound)
+        if bool(nan.any()):
+            # a node without a bound cannot close its tree: its partition stops (UNKNOWN), as in the
+            # native loop (csrc/beta_bab.hip split kernel)
+            bad = np.unique(cur["part"][nan].cpu().numpy())
+            self.stats["nan_nodes"] = self.stats.get("nan_nodes", 0) + int(nan.sum())
+            s.v.status[bad[s.v.status[bad] == RUNNING]] = UNKNOWN
+        return lev, lev.bound >= 0
+
+    def _candidates(self, s: SimpleNamespace, cur, lev, cand: torch.Tensor) -> None:
+        """Vertex pairs of the nodes left open (and the lattice leaves): rigorous point screen, exact check."""
+        if not cand.numel():
+            return
+        be, pa, ra = self.be, s.pa, s.ra
+        xa = lev.xstar[cand].clone()
+        xb = (lev.xpstar[cand] if lev.xpstar is not None else lev.xstar[cand]).clone()
+        if s.relaxed:         # x'_r: its vertex, pulled into [x_r - tau, x_r + tau]
+            xb[:, ra] = clamp_tau(xb[:, ra], xa[:, ra], s.tau)
+        xa[:, pa] = cur["va"][cand]
+        xb[:, pa] = cur["vb"][cand]
+        with self.tm("beta.cand"):
+            alb, aub = be.point_bounds(xa)
+            blb, bub = be.point_bounds(xb)
+        poss = (alb < 0) & (bub > 0)
+        if s.O > 1:       # orientation -1: N(x, va) > 0 > N(x', vb)
+            poss = torch.where(cur["osg"][cand] > 0, poss, (aub > 0) & (blb < 0))
+        ci = cand[poss]
+        if ci.numel():
+            confirm_pairs(s.v, self.q, s.lo_np, s.hi_np, s.mlp_exact, cur["part"][ci].cpu().numpy(), xa[poss], xb[poss])
+
+    def _branch(self, s: SimpleNamespace, cur, lev, closed: torch.Tensor):
+        """Children of the open non-leaf nodes of running partitions within budget (past it: UNKNOWN)."""
+        cfg, v, n0 = self.cfg, s.v, cur["lo"].shape[1]
+        grow = ~closed & ~(lev.split == B.LEAF(n0))
+        grow &= torch.from_numpy(v.status == RUNNING).to(self.dev)[cur["part"]]
+        over = torch.from_numpy(v.nodes >= s.budget).to(self.dev)[cur["part"]] & grow
+        if bool(over.any()):
+            ob = np.unique(cur["part"][over].cpu().numpy())
+            self.stats["over_budget"] = self.stats.get("over_budget", 0) + int((v.status[ob] == RUNNING).sum())
+            v.status[ob] = UNKNOWN
+            grow &= ~over
+        gi = torch.nonzero(grow).flatten()
+        bi = lev.binit[gi] if cfg.warm_beta else torch.zeros_like(lev.binit[gi])
+        split = lev.split[gi]
+        if cfg.branch == "lpgap" and gi.numel():
+            ns = self._lp_gap_split(cur, gi, lev, s.pa, s.ra, s.tau, s.NH)
+            moved = (split >= 0) & (ns >= 0) & (ns != split)
+            split = torch.where(moved, ns, split)
+            bi = torch.where(moved[:, None], torch.zeros_like(bi), bi)   # new neuron: beta from 0
+        if cfg.input_every > 0 and gi.numel():
+            split = self._force_input(cur, gi, split, s.pa, s.ra, n0, cfg.input_every)
+        return self._children({kk: t[gi] for kk, t in cur.items()}, split, bi, s.NH, n0)
 
     def _batched(self) -> bool:
         """The two-phase level (BetaConfig.batched): on, a HIP device, and the network fits."""
@@ -442,20 +428,16 @@ class BetaBaBSolver:
                 and cfg.branch in ("kernel", "pgap") and cfg.input_every == 0
                 and (O == 2 or not self.q.relaxed))
 
-    def _solve_native(self, pool, R0: int, status, lo_np, hi_np, mlp_exact, budget: int, probe_at: int,
-                      time_budget: float, pre_closed=None):
-        """The level loop on the device (csrc/beta_runtime.cpp): the roots of ``pool`` go to the native
-        runtime's node pool; verdicts, witnesses and per-partition node counts come back."""
+    def _solve_native(self, s: SimpleNamespace, time_budget: float) -> BaBResult:
+        """The level loop on the device (csrc/beta_runtime.cpp), started from the roots of ``s.pool``."""
         from ..ops import ext
         from ..ops.hip import _beta_wt, _net
         from .rtpool import checkout
 
         be, q, cfg = self.be, self.q, self.cfg
-        P, n0 = lo_np.shape
-        NH = be.n_hidden
-        relaxed = q.relaxed
-        ra = list(q.ra_idx) if relaxed else []
-        tau = float(q.tau) if relaxed else 0.0
+        pool, R0, status, lo_np, hi_np = s.pool, s.R0, s.v.status, s.lo_np, s.hi_np
+        P = len(lo_np)
+        relaxed, ra, tau = s.relaxed, s.ra, (s.tau if s.relaxed else 0.0)
         i32 = lambda x: x.to(torch.int32).contiguous()  # noqa: E731
         f32 = lambda x: x.to(torch.float32).contiguous()  # noqa: E731
         arrs = [i32(pool["part"]), pool["osg"].to(torch.int8).contiguous(), f32(pool["lo"]), f32(pool["hi"]),
@@ -475,7 +457,7 @@ class BetaBaBSolver:
                 "tighten": int(bool(cfg.tighten)), "feas_iters": int(cfg.feas_iters),
                 "batched": int(self._batched()), "batched_feas": int(self._batched_feas())}
 
-        confirm = exact.make_confirm(mlp_exact, lo_np, hi_np, q)
+        confirm = exact.make_confirm(s.mlp_exact, lo_np, hi_np, q)
         cap = int(max(cfg.max_pool, 2 * R0))
         batch = int(min(cfg.batch_nodes, 32768))
         key = (tuple(q.pa_idx), tuple(ra), tau, batch)
@@ -488,9 +470,9 @@ class BetaBaBSolver:
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         with self.tm("beta.native"), checkout(be, "_beta_rt", key, cap, make) as rt:
             st, cx, cxp, nodes, stats = rt.solve(ptrs, int(R0), status.astype(np.int8), tree_part,
-                                                 lo_np.astype(np.float32), hi_np.astype(np.float32), int(budget),
-                                                 int(probe_at), float(time_budget), cfgd, confirm, stream,
-                                                 np.zeros(P, np.int32) if pre_closed is None else pre_closed)
+                                                 lo_np.astype(np.float32), hi_np.astype(np.float32), int(s.budget),
+                                                 int(s.probe_at), float(time_budget), cfgd, confirm, stream,
+                                                 s.pre_closed)
         stats = dict(stats)
         if os.environ.get("FAIRIFY_BETA_CHECK") and int(stats["levels"]) == 1 and \
                 int((np.asarray(st) == UNSAT).sum()) == int((status == RUNNING).sum()) > 0:
@@ -504,29 +486,20 @@ class BetaBaBSolver:
                   f"t={np.unique(c(pool['t']).numpy())[:4].tolist()} "
                   f"box_w={float((c(pool['hi']) - c(pool['lo'])).sum(1).min())} stats={stats}",
                   file=sys.stderr, flush=True)
-            # the same roots through the torch loop's kernel call (one level, fresh tensors)
-            lev = be.beta_level(pool["lo"], pool["hi"], list(q.pa_idx), pool["va"], pool["vb"], pool["LBA"],
-                                pool["UBA"], pool["LBB"], pool["UBB"], pool["phA"], pool["phB"],
-                                pool["alA"].clone(), pool["alB"].clone(), pool["beA"].clone(), pool["beB"].clone(),
-                                pool["t"].clone(), cfg.root_iters, cfg.lr_a, cfg.lr_b, cfg.lr_t, cfg.decay,
-                                cfg.lookahead, cfg.beta_pos,
-                                (torch.zeros(n0, dtype=torch.bool, device=self.dev).index_fill_(
-                                    0, torch.tensor(ra, dtype=torch.long, device=self.dev), True) if ra else None,
-                                 pool["plo"], pool["phi"], tau, pool["gP"].clone(), pool["gM"].clone())
-                                if relaxed else None,
-                                pgap=cfg.pgap_weights if cfg.branch == "pgap" else 0, osg=pool["osg"])
+            # the same roots through the loop's kernel call, fresh parameters (relaxed implies RA dims: mask s.ram)
+            fresh = {**pool, **{kk: pool[kk].clone() for kk in ("alA", "alB", "beA", "beB", "t", "gP", "gM")}}
+            lev = self._level(s, fresh, True, pool["osg"])
             b = lev.bound.cpu()
             print(f"[beta-check] torch-call root bounds: closed {int((b >= 0).sum())} of {b.numel()}, "
                   f"min {float(b.min()):.4g}", file=sys.stderr, flush=True)
         del arrs
         self.stats["levels"] = self.stats.get("levels", 0) + int(stats["levels"])
         self.stats["nodes"] = self.stats.get("nodes", 0) + int(stats["nodes"])
-        if stats.get("probe_stop"):
-            self.stats["probe_stop"] = self.stats.get("probe_stop", 0) + int(stats["probe_stop"])
-        for key in ("nan_nodes", "root_skip_status", "root_skip_tau", "unclosed", "dev_next"):
+        for key in ("probe_stop", "nan_nodes", "root_skip_status", "root_skip_tau", "unclosed", "dev_next"):
             if stats.get(key):
                 self.stats[key] = self.stats.get(key, 0) + int(stats[key])
-        return (np.asarray(st, dtype=np.int8), np.asarray(cx), np.asarray(cxp), np.asarray(nodes, dtype=np.int64))
+        return BaBResult(np.asarray(st, dtype=np.int8), np.asarray(cx), np.asarray(cxp),
+                         np.asarray(nodes, dtype=np.int64))
 
     def _probe(self, pool, nodes_np, probed, probe_at: int, R0: int, tree_run, status, pre_closed=None) -> None:
         """Partitions past the probe point with no closed pair tree end UNKNOWN (their nodes are
@@ -624,7 +597,7 @@ class BetaBaBSolver:
         xa = lev.xstar[gi].clone().to(be.dtype)
         xb = (lev.xpstar[gi] if lev.xpstar is not None else lev.xstar[gi]).clone().to(be.dtype)
         if ra:
-            xb[:, ra] = torch.minimum(torch.maximum(xb[:, ra], xa[:, ra] - tau), xa[:, ra] + tau)
+            xb[:, ra] = clamp_tau(xb[:, ra], xa[:, ra], tau)
         xa[:, pa] = cur["va"][gi].to(be.dtype)
         xb[:, pa] = cur["vb"][gi].to(be.dtype)
         scores = []
@@ -666,15 +639,3 @@ class BetaBaBSolver:
         best, d = W.max(dim=1)
         use = sel & (best >= 1.0)
         return torch.where(use, (-1 - d).to(split.dtype), split)
-
-    def _confirm(self, parts, xa, xb, status, cex_x, cex_xp, mlp_exact, lo_np, hi_np):
-        X = xa.cpu().numpy().round().astype(np.int64)
-        XP = xb.cpu().numpy().round().astype(np.int64)
-        ok = exact.check_pair_constraints(X, XP, lo_np[parts], hi_np[parts], self.q.pa_idx, self.q.ra_idx, self.q.tau)
-        viol = exact.is_violation(mlp_exact, X, XP) & ok
-        order = np.lexsort(tuple(np.concatenate([X, XP], axis=1).T[::-1]) + (parts,))
-        for k in order:
-            p = parts[k]
-            if viol[k] and status[p] != SAT:
-                status[p] = SAT
-                cex_x[p], cex_xp[p] = X[k], XP[k]

@@ -28,12 +28,13 @@ from ..utils import faults
 from ..utils.timer import StageTimer
 from . import exact
 from . import prune as P_
-from .bab import RUNNING, SAT, UNKNOWN, UNSAT, BaBConfig, BaBSolver, _pa_table
+from .bab import RUNNING, SAT, UNKNOWN, UNSAT, BaBConfig, BaBSolver
 from .beta_bab import BetaBaBSolver, BetaConfig
 from .beta_bab import supported as _beta_supported
 from .falsify import residual_falsify
 from .relu_bab import ReluBaBSolver, ReluConfig
 from .relu_bab import supported as _relu_supported
+from .search import pa_table
 from .sim import simulate
 
 # node expansions per stage (core["stage_nodes"] columns): input-split BaB with its escalation, the
@@ -58,7 +59,7 @@ class GroupState:
         self.ids, self.lo_np, self.hi_np = ids, lo_np, hi_np
         dev = self.dev = be.device
         self.sync = (lambda: torch.cuda.current_stream(dev).synchronize()) if dev.type == "cuda" else (lambda: None)
-        self.values_np, self.pairs_np = _pa_table(q, lo_np, hi_np)
+        self.values_np, self.pairs_np = pa_table(q, lo_np, hi_np)
         self.values = torch.from_numpy(self.values_np).to(dev)
         self.pairs = torch.from_numpy(self.pairs_np).to(dev)
         self.pids = torch.from_numpy(ids).to(dev)
@@ -334,7 +335,7 @@ def _beta_round(s: GroupState, unk: np.ndarray, budget: int, time_budget: float,
     expanded 2 x ``beta_probe_levels`` nodes per pair tree with none of its trees closed (BetaConfig)."""
     branch, iters = cfg.beta_branch, cfg.beta_iters
     if branch == "auto":
-        _, pairs = _pa_table(s.q, s.lo_np[unk[:1]], s.hi_np[unk[:1]])
+        _, pairs = pa_table(s.q, s.lo_np[unk[:1]], s.hi_np[unk[:1]])
         branch, iters = ("pgap", cfg.beta_iters) if pairs.shape[0] <= 2 else ("kernel", 64)
     bs = BetaBaBSolver(s.be, s.q, BetaConfig(
         node_budget=budget, batch_nodes=min(cfg.batch_nodes, 32768), time_budget=time_budget,

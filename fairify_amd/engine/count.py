@@ -29,7 +29,7 @@ from ..ops import rate as R
 from ..ops.backend import Backend
 from ..spec import ResolvedQuery
 from ..utils.timer import NULL, StageTimer
-from .bab import _pa_table, pa_groups
+from .search import pa_groups, pa_table
 from .rate import exact_flags
 
 NODE_BUDGET = 65536
@@ -66,7 +66,7 @@ def witness_pair(mlp, q: ResolvedQuery, lo: np.ndarray, hi: np.ndarray):
     """One exactly confirmed flipping pair (x, x') inside a witness box of :class:`CountResult`
     (an UNFAIR node flips at its first point, a leaf is enumerated), or None."""
     lo, hi = np.asarray(lo, np.int64), np.asarray(hi, np.int64)
-    values, pairs = _pa_table(q, lo[None], hi[None])
+    values, pairs = pa_table(q, lo[None], hi[None])
     free = C.free_dims(q)
     vol = box_weights(q, lo[None], hi[None])[0]
     for s0 in range(0, vol, _WITNESS_CHUNK):
@@ -282,7 +282,7 @@ def count_partitions(be: Backend, q: ResolvedQuery, lo: torch.Tensor, hi: torch.
     for rows in pa_groups(q, lo_np, hi_np):
         if rows.size == 0:
             continue
-        values, pairs = _pa_table(q, lo_np[rows], hi_np[rows])
+        values, pairs = pa_table(q, lo_np[rows], hi_np[rows])
         sel = torch.from_numpy(rows).to(lo.device)
         f, u, o, nodes, wit = _count_group(be, q, lo[sel].to(dev), hi[sel].to(dev), values, pairs, node_budget,
                                            leaf_points, slice_nodes, want[rows], timer, res.stats)

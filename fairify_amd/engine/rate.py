@@ -20,7 +20,7 @@ from ..ops import reference as ref
 from ..ops.backend import Backend
 from ..spec import ResolvedQuery
 from . import exact
-from .bab import _pa_table, pa_groups
+from .search import pa_groups, pa_table
 
 
 @dataclass
@@ -78,7 +78,7 @@ def _profiles(lo_np, hi_np, pid: int, idx: np.ndarray, seed: int) -> np.ndarray:
 def first_exact_pair(mlp, q: ResolvedQuery, lo_np: np.ndarray, hi_np: np.ndarray, pid: int, n_samples: int,
                      seed: int):
     """One exactly confirmed flipping pair (x, x') among the sampled profiles of a partition, or None."""
-    values, pairs = _pa_table(q, lo_np[None], hi_np[None])
+    values, pairs = pa_table(q, lo_np[None], hi_np[None])
     X = _profiles(lo_np, hi_np, pid, np.arange(n_samples), seed)
     flags, x, xp = exact_flags(mlp, q, X, values, pairs, return_pairs=True)
     hit = np.nonzero(flags)[0]
@@ -106,7 +106,7 @@ def measure_partitions(be: Backend, q: ResolvedQuery, lo: torch.Tensor, hi: torc
     for rows in pa_groups(q, lo_np, hi_np):
         if rows.size == 0:
             continue
-        values, pairs = _pa_table(q, lo_np[rows], hi_np[rows])
+        values, pairs = pa_table(q, lo_np[rows], hi_np[rows])
         sel = torch.from_numpy(rows).to(lo.device)
         lo_g, hi_g, pid_g = lo[sel].to(dev), hi[sel].to(dev), pids[sel].to(dev)
         vt, pt = torch.from_numpy(values).to(dev), torch.from_numpy(pairs).to(dev)

@@ -30,15 +30,17 @@ the sound replacement of the floating-point HiGHS MILP UNSAT (smt/milp.py) for t
 CPU measurement on the dumped residue (tools/exp/relu_proto.py): AC-8 38/40 closed with 6
 nodes, AC-12 40/40 with a median of 34 nodes; AC-7 needs more (wide layers, no exact zeros).
 
-The torch path here is the reference semantics (CPU tests); on the GPU the native runtime
-(csrc/relu_runtime.cpp + csrc/relu.hip) runs the same algorithm.
+The torch path here (state ``_PhaseSearch``; bound, certify, candidate and branch steps) is the reference
+semantics (CPU tests); on the GPU the native runtime (csrc/relu_runtime.cpp + csrc/relu.hip) runs the same
+algorithm.  The verdict arrays, confirmation, PA-group scatter and orientation merge are engine/search.py's.
 """
 from __future__ import annotations
 
 import os
 import time
 from dataclasses import dataclass
-from typing import List, Optional
+from types import SimpleNamespace
+from typing import Optional
 
 import numpy as np
 import torch
@@ -49,7 +51,8 @@ from ..ops.backend import Backend
 from ..spec import ResolvedQuery
 from ..utils.timer import NULL, StageTimer
 from . import exact
-from .bab import RUNNING, SAT, UNKNOWN, UNSAT, BaBResult, _pa_table, pa_groups
+from .search import (RUNNING, UNKNOWN, UNSAT, BaBResult, Verdicts, clamp_tau, confirm_pairs, halve,
+                     merge_orientations, pa_groups, pa_table, pool_overflow, solve_pa_groups, tau_apart)
 
 
 @dataclass
@@ -161,12 +164,45 @@ def _pick_form(res_c, res_0, res_e, fw_low, cr):
     return (torch.where(use, lam, res_c), torch.where(use[:, 0], c, res_0), torch.where(use[:, 0], err, res_e))
 
 
+class _PhaseSearch:
+    """State of the torch level loop over one PA group: the PA table, the free / shared input dims, the
+    verdicts and the pool, a root per (RUNNING partition, ordered pair).  A node: partition, pair, x box,
+    x' box of the RA dims [N, len(ra)] (no columns unless relaxed), phases of the two copies [N, 2, Nh]."""
+    POOL = ("part", "pair", "lo", "hi", "plo", "phi", "phase")
+
+    def __init__(self, sol: "ReluBaBSolver", lo_np, hi_np, v: Verdicts, values_np, pairs_np):
+        dev, dt, q = sol.dev, sol.be.dtype, sol.q
+        self.v, self.lo_np, self.hi_np = v, lo_np, hi_np
+        self.pa, self.relaxed, self.tau = list(q.pa_idx), q.relaxed, float(q.tau)
+        self.ra = list(q.ra_idx) if q.relaxed else []
+        self.values = torch.from_numpy(values_np).to(dev, dt)
+        self.pairs = torch.from_numpy(pairs_np).to(dev)
+        self.free = torch.ones(lo_np.shape[1], dtype=dt, device=dev)
+        self.free[self.pa] = 0
+        self.shared = self.free.clone()
+        self.shared[self.ra] = 0
+        run, Pp = np.nonzero(v.status == RUNNING)[0], pairs_np.shape[0]
+        self.part = torch.from_numpy(np.repeat(run, Pp)).to(dev)
+        self.pair = torch.arange(Pp, device=dev).repeat(len(run))
+        self.lo = torch.from_numpy(lo_np).to(dev, dt)[self.part]
+        self.hi = torch.from_numpy(hi_np).to(dev, dt)[self.part]
+        # relaxed: the x' coordinates of the RA dims, unclipped, [lo - tau, hi + tau]
+        none = torch.zeros(len(self.part), 0, dtype=dt, device=dev)
+        self.plo = (self.lo[:, self.ra] - self.tau) if q.relaxed else none
+        self.phi = (self.hi[:, self.ra] + self.tau) if q.relaxed else none
+        self.phase = torch.zeros(len(self.part), 2, sol.be.n_hidden, dtype=torch.int8, device=dev)
+
+    def keep(self, sel) -> None:
+        for k in self.POOL:
+            setattr(self, k, getattr(self, k)[sel])
+
+    def running(self) -> torch.Tensor:
+        return torch.from_numpy(self.v.status == RUNNING).to(self.part.device)[self.part]
+
+
 class ReluBaBSolver:
     def __init__(self, backend: Backend, query: ResolvedQuery, cfg: ReluConfig, timer: StageTimer = NULL):
-        self.be = backend
-        self.q = query
-        self.cfg = cfg
-        self.tm = timer
+        self.be, self.q, self.cfg, self.tm = backend, query, cfg, timer
         self.dev = backend.device
         self.stats = {}
 
@@ -177,30 +213,24 @@ class ReluBaBSolver:
         (:func:`negated`); a partition is UNSAT when both close, SAT when either finds a pair (always
         confirmed exactly on ``mlp_exact``, whose violation test is orientation-free)."""
         t0 = time.time()
-        P, n = lo_np.shape
-        status = np.full(P, RUNNING, dtype=np.int8) if init_status is None else init_status.astype(np.int8).copy()
+        v = Verdicts(*lo_np.shape, init_status)
         if not supported(self.q):
-            status[status == RUNNING] = UNKNOWN
-            return BaBResult(status, np.zeros((P, n), np.int64), np.zeros((P, n), np.int64), np.zeros(P, np.int64))
-        if self.q.relaxed and not getattr(self, "_second", False) and not self._merged():
-            r1 = self._solve_groups_all(lo_np, hi_np, mlp_exact, status, t0)
-            closed = (r1.status == UNSAT) & (status == RUNNING)
-            if not closed.any():
-                return r1
-            neg = ReluBaBSolver(Backend(negated(self.be.mlp), device=self.dev), self.q,
-                                ReluConfig(node_budget=self.cfg.node_budget, batch_nodes=self.cfg.batch_nodes,
-                                           time_budget=max(0.0, self.cfg.time_budget - (time.time() - t0)),
-                                           max_pool=self.cfg.max_pool), timer=self.tm)
+            return v.close_running(UNKNOWN).result()
+        r1 = solve_pa_groups(pa_groups(self.q, lo_np, hi_np), lo_np, hi_np, v.status, self.cfg.time_budget, t0,
+                             lambda g, st, left: self._solve_group(lo_np[g], hi_np[g], mlp_exact, st, left))
+        if not self.q.relaxed or getattr(self, "_second", False) or self._merged():
+            return r1
+
+        def second(st2):
+            # four fields of this config only: refine and merge_orient take their environment defaults
+            c = self.cfg
+            cfg = ReluConfig(node_budget=c.node_budget, batch_nodes=c.batch_nodes, max_pool=c.max_pool,
+                             time_budget=max(0.0, c.time_budget - (time.time() - t0)))
+            neg = ReluBaBSolver(Backend(negated(self.be.mlp), device=self.dev), self.q, cfg, timer=self.tm)
             neg._second = True
-            st2 = np.where(closed, RUNNING, UNKNOWN).astype(np.int8)
-            r2 = neg.solve(lo_np, hi_np, mlp_exact, init_status=st2)
-            out = r1.status.copy()
-            out[closed] = r2.status[closed]                 # UNSAT only if the second closed too
-            cx, cxp = r1.cex_x.copy(), r1.cex_xp.copy()
-            s2 = closed & (r2.status == SAT)
-            cx[s2], cxp[s2] = r2.cex_x[s2], r2.cex_xp[s2]
-            return BaBResult(out, cx, cxp, r1.nodes + r2.nodes, 0, time.time() - t0)
-        return self._solve_groups_all(lo_np, hi_np, mlp_exact, status, t0)
+            return neg.solve(lo_np, hi_np, mlp_exact, init_status=st2)
+
+        return merge_orientations(r1, v.status, second, t0)
 
     def _native(self) -> bool:
         torch_rx = self.q.relaxed and os.environ.get("FAIRIFY_RELU_RELAXED_TORCH") == "1"
@@ -210,22 +240,9 @@ class ReluBaBSolver:
         """Relaxed query, both orientations in the native runtime's one search."""
         return self.q.relaxed and self.cfg.merge_orient and self._native()
 
-    def _solve_groups_all(self, lo_np, hi_np, mlp_exact, status, t0) -> BaBResult:
-        P, n = lo_np.shape
-        status = status.copy()
-        groups = pa_groups(self.q, lo_np, hi_np)
-        cex_x = np.zeros((P, n), dtype=np.int64)
-        cex_xp = np.zeros((P, n), dtype=np.int64)
-        nodes = np.zeros(P, dtype=np.int64)
-        for g in groups:
-            left = max(0.0, self.cfg.time_budget - (time.time() - t0))
-            st, cx, cxp, nd = self._solve_group(lo_np[g], hi_np[g], mlp_exact, status[g], left)
-            status[g], cex_x[g], cex_xp[g], nodes[g] = st, cx, cxp, nd
-        return BaBResult(status, cex_x, cex_xp, nodes, 0, time.time() - t0)
-
     # ------------------------------------------------------------------------------------------
-    def _solve_group(self, lo_np, hi_np, mlp_exact, status, time_budget):
-        values_np, pairs_np = _pa_table(self.q, lo_np, hi_np)
+    def _solve_group(self, lo_np, hi_np, mlp_exact, status, time_budget) -> BaBResult:
+        values_np, pairs_np = pa_table(self.q, lo_np, hi_np)
         # the native runtime (csrc/relu_runtime.cpp) on the GPU, PA-only and relaxed queries alike
         # (relaxed: an x' RA box per node; the second orientation is solve()'s negated network);
         # FAIRIFY_TORCH_BAB=1: the torch orchestration (the reference semantics of the CPU tests)
@@ -234,219 +251,167 @@ class ReluBaBSolver:
             return self._solve_native(lo_np, hi_np, mlp_exact, status, values_np, pairs_np, time_budget)
         return self._solve_torch(lo_np, hi_np, mlp_exact, status, values_np, pairs_np, time_budget)
 
-    def _solve_torch(self, lo_np, hi_np, mlp_exact, status, values_np, pairs_np, time_budget):
-        t0 = time.time()
-        be, q, cfg = self.be, self.q, self.cfg
-        dev, dt = self.dev, self.be.dtype
-        P, n0 = lo_np.shape
-        Nh = be.n_hidden
-        pa = list(q.pa_idx)
-        status = status.copy()
-        cex_x = np.zeros((P, n0), dtype=np.int64)
-        cex_xp = np.zeros((P, n0), dtype=np.int64)
-        nodes_np = np.zeros(P, dtype=np.int64)
-        Pp = pairs_np.shape[0]
-        run = np.nonzero(status == RUNNING)[0]
-        if Pp == 0:
-            status[run] = UNSAT
-            return status, cex_x, cex_xp, nodes_np
-        values = torch.from_numpy(values_np).to(dev, dt)
-        pairs = torch.from_numpy(pairs_np).to(dev)
-        free = torch.ones(n0, dtype=dt, device=dev)
-        free[pa] = 0
-        relaxed = q.relaxed
-        ra = list(q.ra_idx) if relaxed else []
-        tau = float(q.tau)
-        shared = free.clone()
-        shared[ra] = 0
-        # one root per (partition, ordered pair)
-        part = torch.from_numpy(np.repeat(run, Pp)).to(dev)
-        pair = torch.arange(Pp, device=dev).repeat(len(run))
-        lo = torch.from_numpy(lo_np).to(dev, dt)[part]
-        hi = torch.from_numpy(hi_np).to(dev, dt)[part]
-        # relaxed: the x' coordinates of the RA dims, unclipped, [lo - tau, hi + tau]
-        plo = (lo[:, ra] - tau) if relaxed else torch.zeros(len(part), 0, dtype=dt, device=dev)
-        phi = (hi[:, ra] + tau) if relaxed else torch.zeros(len(part), 0, dtype=dt, device=dev)
-        phase = torch.zeros(len(part), 2, Nh, dtype=torch.int8, device=dev)
-        levels = 0
-        timed_out = False
-        while part.numel():
+    def _solve_torch(self, lo_np, hi_np, mlp_exact, status, values_np, pairs_np, time_budget) -> BaBResult:
+        t0, cfg = time.time(), self.cfg
+        v = Verdicts(*lo_np.shape, status)
+        if pairs_np.shape[0] == 0:
+            return v.close_running(UNSAT).result()
+        s = _PhaseSearch(self, lo_np, hi_np, v, values_np, pairs_np)
+        levels, timed_out = 0, False
+        while s.part.numel():
             if time.time() - t0 > time_budget:
                 timed_out = True
                 break
             levels += 1
-            N = part.numel()
-            alive = torch.from_numpy(status == RUNNING).to(dev)[part]
-            if relaxed:      # x_r and x'_r boxes more than tau apart: no admissible pair, node closed
-                alive &= ~((plo > hi[:, ra] + tau) | (phi < lo[:, ra] - tau)).any(dim=1)
+            alive = s.running()
+            if s.relaxed:      # x_r and x'_r boxes more than tau apart: no admissible pair, node closed
+                alive &= ~tau_apart(s.lo[:, s.ra], s.hi[:, s.ra], s.plo, s.phi, s.tau)
             if not bool(alive.all()):
-                part, pair, lo, hi, phase = part[alive], pair[alive], lo[alive], hi[alive], phase[alive]
-                plo, phi = plo[alive], phi[alive]
-                N = part.numel()
-                if N == 0:
+                s.keep(alive)
+                if s.part.numel() == 0:
                     break
-            np.add.at(nodes_np, part.cpu().numpy(), 1)
-            vA, vB = pairs[pair, 0], pairs[pair, 1]
-            rlo = lo.repeat_interleave(2, dim=0)
-            rhi = hi.repeat_interleave(2, dim=0)
-            rv = torch.stack([vA, vB], dim=1).reshape(-1)
-            rlo[:, pa] = values[rv]
-            rhi[:, pa] = values[rv]
-            if relaxed:          # copy B reads x' on the RA dims
-                rlo[1::2, ra] = plo
-                rhi[1::2, ra] = phi
-            rph = phase.reshape(2 * N, Nh)
-            with self.tm("relu.bounds"):
-                res = be.bounds(rlo, rhi, mode="symbolic", keep_layers=True, phase=rph)
-                pc, forms = be.crown_phase(rlo, rhi, res, rph)
-            A, B = slice(0, None, 2), slice(1, None, 2)
-            if forms is None:
-                # HIP kernel: logit bounds intersected, infeasible rows set to (+inf, -inf) and the
-                # tighter input forms written into ``res`` in place
-                olb, oub = res.out_lb.to(dt), res.out_ub.to(dt)
-                LAc, LA0, LAe = res.Lc, res.L0, res.Le
-                UBc, UB0, UBe = res.Uc, res.U0, res.Ue
-            else:
-                olb = torch.maximum(res.out_lb.to(dt), pc.low[:, 0].to(dt))
-                oub = torch.minimum(res.out_ub.to(dt), -pc.low[:, 1].to(dt))
-                inf = res.infeasible if res.infeasible is not None else torch.zeros(2 * N, dtype=torch.bool,
-                                                                                    device=dev)
-                olb = torch.where(inf, torch.full_like(olb, float("inf")), olb)
-                oub = torch.where(inf, torch.full_like(oub, -float("inf")), oub)
-                # coupled certificate on the input forms (the tighter of forward / backward per row)
-                LAc, LA0, LAe = _pick_form(res.Lc, res.L0, res.Le, res.out_lb, forms[1.0])
-                lamU, cU, eU, lowU = forms[-1.0]
-                UBc, UB0, UBe = _pick_form(res.Uc, res.U0, res.Ue, -res.out_ub, (-lamU, -cU, eU, lowU))
-            closed = (olb[A] >= 0) | (oub[B] <= 0)
-            LAc, LA0, LAe = LAc[A], LA0[A], LAe[A]
-            UBc, UB0, UBe = UBc[B], UB0[B], UBe[B]
-            # fold the PA coordinates (fixed per row) into the constants
-            fa_A = (LAc[:, pa] * values[vA]).sum(1)
-            fa_B = (UBc[:, pa] * values[vB]).sum(1)
-            mxb = torch.maximum(lo.abs(), hi.abs())
-            mxb_b = mxb.clone()
-            if relaxed:
-                mxb_b[:, ra] = torch.maximum(plo.abs(), phi.abs())
-            # rounding margin over the folded PA products' magnitudes (with several PA dims their
-            # sum can cancel below the products' errors)
-            MA = (LAc.abs() * mxb * free).sum(1) + (LA0 - LAe).abs() + (LAc[:, pa] * values[vA]).abs().sum(1)
-            MB = (UBc.abs() * mxb_b * free).sum(1) + (UB0 + UBe).abs() + (UBc[:, pa] * values[vB]).abs().sum(1)
-            xpstar = None
-            if relaxed:
-                LAcf, UBcf = LAc * free, UBc * free
-                g, tstar, xstar, xpstar = certify_pair_relaxed(LAcf, LA0 - LAe + fa_A, MA, UBcf, UB0 + UBe + fa_B, MB,
-                                                               lo, hi, plo, phi, shared, ra, be.unit)
-            else:
-                g, tstar, xstar = certify_pair(LAc, LA0 - LAe + fa_A, MA, UBc, UB0 + UBe + fa_B, MB, lo, hi, free,
-                                               be.unit)
-            open_ = ~closed & (g > 0)
-            # ---- candidate vertex pairs of open nodes: rigorous point bounds, then the exact check
-            oi = torch.nonzero(open_).flatten()
-            if oi.numel():
-                xa = xstar[oi].clone()
-                xb = xstar[oi].clone()
-                xa[:, pa] = values[vA[oi]]
-                xb[:, pa] = values[vB[oi]]
-                if relaxed:      # x'_r: its vertex, pulled into [x_r - tau, x_r + tau]
-                    xb[:, ra] = torch.minimum(torch.maximum(xpstar[oi], xa[:, ra] - tau), xa[:, ra] + tau)
-                with self.tm("relu.cand"):
-                    alb, _ = be.point_bounds(xa)
-                    _, bub = be.point_bounds(xb)
-                poss = (alb < 0) & (bub > 0)
-                ci = oi[poss]
-                if ci.numel():
-                    self._confirm(ci, xa[poss], xb[poss], part, status, cex_x, cex_xp, mlp_exact, lo_np, hi_np)
+            np.add.at(v.nodes, s.part.cpu().numpy(), 1)
+            bd = self._bound(s)
+            open_, tstar, xstar, xpstar = self._certify(s, bd)
+            self._candidates(s, bd, torch.nonzero(open_).flatten(), xstar, xpstar, mlp_exact)
             # ---- leaves: the non-PA box (and the x' RA box) is a single lattice point -> decided
             # exactly above
-            width = ((hi - lo) * free).amax(dim=1)
-            if relaxed:
-                width = torch.maximum(width, (phi - plo).amax(dim=1))
-            leaf = open_ & (width == 0)
-            run_t = torch.from_numpy(status == RUNNING).to(dev)[part]
-            grow = open_ & ~leaf & run_t
+            width = ((s.hi - s.lo) * s.free).amax(dim=1)
+            if s.relaxed:
+                width = torch.maximum(width, (s.phi - s.plo).amax(dim=1))
+            grow = open_ & ~(width == 0) & s.running()
             if not bool(grow.any()):
-                break
+                break       # no time-out: whatever is RUNNING has no open node left and closes UNSAT
             # ---- budget: a partition past its node budget with open nodes ends UNKNOWN
-            over = torch.from_numpy(nodes_np >= cfg.node_budget).to(dev)[part] & grow
+            over = torch.from_numpy(v.nodes >= cfg.node_budget).to(self.dev)[s.part] & grow
             if bool(over.any()):
-                status[np.unique(part[over].cpu().numpy())] = UNKNOWN
+                v.status[np.unique(s.part[over].cpu().numpy())] = UNKNOWN
                 grow = grow & ~over
-            gi = torch.nonzero(grow).flatten()
-            # ---- branching: the bound closest to closing, at its best neuron; else an input split
-            gapA = -olb[A][gi]
-            gapB = oub[B][gi]
-            sA = pc.split[A, 0][gi]
-            sB = pc.split[B, 1][gi]
-            useA = (sA >= 0) & ((gapA <= gapB) | (sB < 0))
-            useB = ~useA & (sB >= 0)
-            relu = useA | useB
-            row = torch.where(useA, torch.zeros_like(sA), torch.ones_like(sA))
-            neu = torch.where(useA, sA, sB)
-            ri = gi[relu]
-            cp = phase[ri].repeat(2, 1, 1)
-            k = ri.numel()
-            r2 = row[relu].repeat(2)
-            n2 = neu[relu].repeat(2)
-            cp[torch.arange(2 * k, device=dev), r2, n2] = torch.cat([torch.full((k,), -1, dtype=torch.int8, device=dev),
-                                                                     torch.ones(k, dtype=torch.int8, device=dev)])
-            # input split along the dim of largest |coefficient| x width of the certificate at t*
-            # (relaxed: the x' RA dims compete as extra columns, scored by copy B's coefficient)
-            ii = gi[~relu]
-            c_t = tstar[ii, None] * (-LAc[ii]) + (1 - tstar[ii, None]) * UBc[ii]
-            if relaxed:
-                c_t[:, ra] = tstar[ii, None] * LAc[ii][:, ra]
-            w = (hi[ii] - lo[ii]) * free
-            sc = torch.where(w > 0, c_t.abs() * w + 1e-9 * w, torch.full_like(w, -1.0))
-            if relaxed:
-                wp = phi[ii] - plo[ii]
-                cp_ = (1 - tstar[ii, None]) * UBc[ii][:, ra]
-                sc = torch.cat([sc, torch.where(wp > 0, cp_.abs() * wp + 1e-9 * wp, torch.full_like(wp, -1.0))], dim=1)
-            d = sc.argmax(dim=1)
-            ar = torch.arange(ii.numel(), device=dev)
-            lo1, hi1, lo2, hi2 = lo[ii].clone(), hi[ii].clone(), lo[ii].clone(), hi[ii].clone()
-            plo1, phi1, plo2, phi2 = plo[ii].clone(), phi[ii].clone(), plo[ii].clone(), phi[ii].clone()
-            onx = d < n0
-            if bool(onx.any()):
-                a_, d_ = ar[onx], d[onx]
-                mid = torch.floor((lo[ii][a_, d_] + hi[ii][a_, d_]) / 2)
-                hi1[a_, d_] = mid
-                lo2[a_, d_] = mid + 1
-            if relaxed and bool((~onx).any()):
-                a_, d_ = ar[~onx], d[~onx] - n0
-                mid = torch.floor((plo[ii][a_, d_] + phi[ii][a_, d_]) / 2)
-                phi1[a_, d_] = mid
-                plo2[a_, d_] = mid + 1
-            part = torch.cat([part[ri], part[ri], part[ii], part[ii]])
-            pair = torch.cat([pair[ri], pair[ri], pair[ii], pair[ii]])
-            lo_n = torch.cat([lo[ri], lo[ri], lo1, lo2])
-            hi_n = torch.cat([hi[ri], hi[ri], hi1, hi2])
-            plo = torch.cat([plo[ri], plo[ri], plo1, plo2])
-            phi = torch.cat([phi[ri], phi[ri], phi1, phi2])
-            phase = torch.cat([cp, phase[ii], phase[ii]])
-            lo, hi = lo_n, hi_n
-            if part.numel() > cfg.max_pool:
-                lost = torch.unique(part[cfg.max_pool:]).cpu().numpy()
-                status[lost[status[lost] == RUNNING]] = UNKNOWN
-                part, pair, lo, hi, phase, plo, phi = (t[:cfg.max_pool] for t in (part, pair, lo, hi, phase, plo, phi))
-        left = set(part.cpu().numpy().tolist()) if (timed_out and part.numel()) else set()
-        for p in np.nonzero(status == RUNNING)[0]:
-            status[p] = UNKNOWN if p in left else UNSAT
-        self.stats = {"levels": levels}
-        return status, cex_x, cex_xp, nodes_np
+            self._branch(s, bd, torch.nonzero(grow).flatten(), tstar)
+            if s.part.numel() > cfg.max_pool:
+                pool_overflow(s.part, cfg.max_pool, v.status)
+                s.keep(slice(cfg.max_pool))
+        v.sweep(s.part.cpu().numpy() if timed_out else ())
+        self.stats = {"levels": levels}         # (per group: the last group's)
+        return v.result()
 
-    def _confirm(self, ci, xa, xb, part, status, cex_x, cex_xp, mlp_exact, lo_np, hi_np):
-        X = xa.cpu().numpy().round().astype(np.int64)
-        XP = xb.cpu().numpy().round().astype(np.int64)
-        parts = part[ci].cpu().numpy()
-        ok = exact.check_pair_constraints(X, XP, lo_np[parts], hi_np[parts], self.q.pa_idx, self.q.ra_idx, self.q.tau)
-        viol = exact.is_violation(mlp_exact, X, XP) & ok
-        # each partition's witness: the first confirmed pair in (partition, lexicographic) order
-        order = np.lexsort(tuple(np.concatenate([X, XP], axis=1).T[::-1]) + (parts,))
-        for k in order:
-            p = parts[k]
-            if viol[k] and status[p] != SAT:
-                status[p] = SAT
-                cex_x[p], cex_xp[p] = X[k], XP[k]
+    def _bound(self, s: _PhaseSearch) -> SimpleNamespace:
+        """Phase-fixed bounds of both copies of every node (rows 2k: copy A = N(., v), 2k + 1: copy B = N(., v')):
+        logit bounds of all rows, copy A's lower and copy B's upper input form, the nodes they close."""
+        be, pa, ra = self.be, s.pa, s.ra
+        dt, N = be.dtype, s.part.numel()
+        vA, vB = s.pairs[s.pair, 0], s.pairs[s.pair, 1]
+        rlo, rhi = s.lo.repeat_interleave(2, dim=0), s.hi.repeat_interleave(2, dim=0)
+        rv = torch.stack([vA, vB], dim=1).reshape(-1)
+        rlo[:, pa] = s.values[rv]
+        rhi[:, pa] = s.values[rv]
+        if s.relaxed:          # copy B reads x' on the RA dims
+            rlo[1::2, ra] = s.plo
+            rhi[1::2, ra] = s.phi
+        rph = s.phase.reshape(2 * N, be.n_hidden)
+        with self.tm("relu.bounds"):
+            res = be.bounds(rlo, rhi, mode="symbolic", keep_layers=True, phase=rph)
+            pc, forms = be.crown_phase(rlo, rhi, res, rph)
+        if forms is None:
+            # HIP kernel: logit bounds intersected, infeasible rows set to (+inf, -inf) and the
+            # tighter input forms written into ``res`` in place
+            olb, oub = res.out_lb.to(dt), res.out_ub.to(dt)
+            LA, UB = (res.Lc, res.L0, res.Le), (res.Uc, res.U0, res.Ue)
+        else:
+            olb = torch.maximum(res.out_lb.to(dt), pc.low[:, 0].to(dt))
+            oub = torch.minimum(res.out_ub.to(dt), -pc.low[:, 1].to(dt))
+            inf = res.infeasible
+            if inf is None:
+                inf = torch.zeros(2 * N, dtype=torch.bool, device=self.dev)
+            olb = torch.where(inf, torch.full_like(olb, float("inf")), olb)
+            oub = torch.where(inf, torch.full_like(oub, -float("inf")), oub)
+            # coupled certificate on the input forms (the tighter of forward / backward per row)
+            LA = _pick_form(res.Lc, res.L0, res.Le, res.out_lb, forms[1.0])
+            lamU, cU, eU, lowU = forms[-1.0]
+            UB = _pick_form(res.Uc, res.U0, res.Ue, -res.out_ub, (-lamU, -cU, eU, lowU))
+        A, B = slice(0, None, 2), slice(1, None, 2)
+        return SimpleNamespace(vA=vA, vB=vB, pc=pc, olb=olb, oub=oub, closed=(olb[A] >= 0) | (oub[B] <= 0),
+                               LAc=LA[0][A], LA0=LA[1][A], LAe=LA[2][A], UBc=UB[0][B], UB0=UB[1][B], UBe=UB[2][B])
+
+    def _certify(self, s: _PhaseSearch, bd: SimpleNamespace):
+        """The coupled pair certificate: (open mask, t*, the vertex x* and, relaxed, x'* on the RA dims)."""
+        pa, ra, free, values, unit = s.pa, s.ra, s.free, s.values, self.be.unit
+        LAc, LA0, LAe, UBc, UB0, UBe = bd.LAc, bd.LA0, bd.LAe, bd.UBc, bd.UB0, bd.UBe
+        # fold the PA coordinates (fixed per row) into the constants
+        fa_A = (LAc[:, pa] * values[bd.vA]).sum(1)
+        fa_B = (UBc[:, pa] * values[bd.vB]).sum(1)
+        mxb = torch.maximum(s.lo.abs(), s.hi.abs())
+        mxb_b = mxb.clone()
+        if s.relaxed:
+            mxb_b[:, ra] = torch.maximum(s.plo.abs(), s.phi.abs())
+        # rounding margin over the folded PA products' magnitudes (with several PA dims their
+        # sum can cancel below the products' errors)
+        MA = (LAc.abs() * mxb * free).sum(1) + (LA0 - LAe).abs() + (LAc[:, pa] * values[bd.vA]).abs().sum(1)
+        MB = (UBc.abs() * mxb_b * free).sum(1) + (UB0 + UBe).abs() + (UBc[:, pa] * values[bd.vB]).abs().sum(1)
+        xpstar = None
+        if s.relaxed:
+            g, tstar, xstar, xpstar = certify_pair_relaxed(LAc * free, LA0 - LAe + fa_A, MA, UBc * free,
+                                                           UB0 + UBe + fa_B, MB, s.lo, s.hi, s.plo, s.phi, s.shared,
+                                                           ra, unit)
+        else:
+            g, tstar, xstar = certify_pair(LAc, LA0 - LAe + fa_A, MA, UBc, UB0 + UBe + fa_B, MB, s.lo, s.hi, free, unit)
+        return ~bd.closed & (g > 0), tstar, xstar, xpstar
+
+    def _candidates(self, s: _PhaseSearch, bd: SimpleNamespace, oi: torch.Tensor, xstar, xpstar, mlp_exact) -> None:
+        """Candidate vertex pairs of the open nodes ``oi``: rigorous point bounds, then the exact check."""
+        if not oi.numel():
+            return
+        xa, xb = xstar[oi].clone(), xstar[oi].clone()
+        xa[:, s.pa] = s.values[bd.vA[oi]]
+        xb[:, s.pa] = s.values[bd.vB[oi]]
+        if s.relaxed:      # x'_r: its vertex, pulled into [x_r - tau, x_r + tau]
+            xb[:, s.ra] = clamp_tau(xpstar[oi], xa[:, s.ra], s.tau)
+        with self.tm("relu.cand"):
+            alb, _ = self.be.point_bounds(xa)
+            _, bub = self.be.point_bounds(xb)
+        poss = (alb < 0) & (bub > 0)
+        ci = oi[poss]
+        if ci.numel():
+            confirm_pairs(s.v, self.q, s.lo_np, s.hi_np, mlp_exact, s.part[ci].cpu().numpy(), xa[poss], xb[poss])
+
+    def _branch(self, s: _PhaseSearch, bd: SimpleNamespace, gi: torch.Tensor, tstar) -> None:
+        """Next level, two children per node of ``gi``: a phase split of the bound closest to closing at its
+        best neuron, or, where no unstable neuron is left, an input split."""
+        dev, n0, ra = self.dev, s.lo.shape[1], s.ra
+        A, B = slice(0, None, 2), slice(1, None, 2)
+        gapA, gapB = -bd.olb[A][gi], bd.oub[B][gi]
+        sA, sB = bd.pc.split[A, 0][gi], bd.pc.split[B, 1][gi]
+        useA = (sA >= 0) & ((gapA <= gapB) | (sB < 0))
+        useB = ~useA & (sB >= 0)
+        relu = useA | useB
+        row = torch.where(useA, torch.zeros_like(sA), torch.ones_like(sA))
+        neu = torch.where(useA, sA, sB)
+        ri = gi[relu]
+        cp, k = s.phase[ri].repeat(2, 1, 1), ri.numel()
+        cp[torch.arange(2 * k, device=dev), row[relu].repeat(2), neu[relu].repeat(2)] = torch.cat(
+            [torch.full((k,), -1, dtype=torch.int8, device=dev), torch.ones(k, dtype=torch.int8, device=dev)])
+        # input split along the dim of largest |coefficient| x width of the certificate at t*
+        # (relaxed: the x' RA dims compete as extra columns, scored by copy B's coefficient)
+        ii = gi[~relu]
+        c_t = tstar[ii, None] * (-bd.LAc[ii]) + (1 - tstar[ii, None]) * bd.UBc[ii]
+        if s.relaxed:
+            c_t[:, ra] = tstar[ii, None] * bd.LAc[ii][:, ra]
+        w = (s.hi[ii] - s.lo[ii]) * s.free
+        sc = torch.where(w > 0, c_t.abs() * w + 1e-9 * w, torch.full_like(w, -1.0))
+        if s.relaxed:
+            wp = s.phi[ii] - s.plo[ii]
+            cp_ = (1 - tstar[ii, None]) * bd.UBc[ii][:, ra]
+            sc = torch.cat([sc, torch.where(wp > 0, cp_.abs() * wp + 1e-9 * wp, torch.full_like(wp, -1.0))], dim=1)
+        d = sc.argmax(dim=1)
+        ar = torch.arange(ii.numel(), device=dev)
+        onx = d < n0
+        lo1, hi1, lo2, hi2 = halve(s.lo[ii], s.hi[ii], ar[onx], d[onx])
+        plo1, phi1, plo2, phi2 = halve(s.plo[ii], s.phi[ii], ar[~onx], d[~onx] - n0)
+        s.part = torch.cat([s.part[ri], s.part[ri], s.part[ii], s.part[ii]])
+        s.pair = torch.cat([s.pair[ri], s.pair[ri], s.pair[ii], s.pair[ii]])
+        s.lo, s.hi = torch.cat([s.lo[ri], s.lo[ri], lo1, lo2]), torch.cat([s.hi[ri], s.hi[ri], hi1, hi2])
+        s.plo, s.phi = torch.cat([s.plo[ri], s.plo[ri], plo1, plo2]), torch.cat([s.phi[ri], s.phi[ri], phi1, phi2])
+        s.phase = torch.cat([cp, s.phase[ii], s.phase[ii]])
 
     # ------------------------------------------------------------------------------------------
     def _runtime(self, values_np: np.ndarray, pairs_np: np.ndarray, n_root: int):
@@ -473,26 +438,23 @@ class ReluBaBSolver:
         return checkout(self.be, "_relu_rt", key, max(self.cfg.max_pool, 2 * n_root), make)
 
     def _solve_native(self, lo_np, hi_np, mlp_exact, status, values_np, pairs_np, time_budget):
-        P, n0 = lo_np.shape
         from ..ops import ext
         from ..ops.hip import _net
 
+        v = Verdicts(*lo_np.shape, status)
         if not ext().relu_fits(_net(self.be)):
             # the phase kernel cannot hold this network (a layer > 256 wide or > 160 KB of LDS):
             # the stage is skipped, its partitions stay UNKNOWN for the later stages
-            status = status.copy()
-            status[status == RUNNING] = UNKNOWN
-            return status, np.zeros((P, n0), np.int64), np.zeros((P, n0), np.int64), np.zeros(P, np.int64)
+            return v.close_running(UNKNOWN).result()
         no = 2 if self._merged() else 1
         n_root = int((status == RUNNING).sum()) * max(1, pairs_np.shape[0]) * no
         if pairs_np.shape[0] == 0:
-            status = status.copy()
-            status[status == RUNNING] = UNSAT
-            return status, np.zeros((P, n0), np.int64), np.zeros((P, n0), np.int64), np.zeros(P, np.int64)
+            return v.close_running(UNSAT).result()
         confirm = exact.make_confirm(mlp_exact, lo_np, hi_np, self.q)
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         with self.tm("relu.native"), self._runtime(values_np, pairs_np, n_root) as rt:
             st, cx, cxp, nodes, stats = rt.solve(lo_np.astype(np.float32), hi_np.astype(np.float32), status,
                                                  int(self.cfg.node_budget) * no, float(time_budget), confirm, stream)
         self.stats = dict(stats)
-        return (np.asarray(st, dtype=np.int8), np.asarray(cx), np.asarray(cxp), np.asarray(nodes, dtype=np.int64))
+        return BaBResult(np.asarray(st, dtype=np.int8), np.asarray(cx), np.asarray(cxp),
+                         np.asarray(nodes, dtype=np.int64))

@@ -108,11 +108,11 @@ def walk(be, q, lo, hi, leaf_points, max_levels=64):
     """The level loop written out with the ops/count.py reference pieces (no budget, nothing
     enumerated): per level the node pool with its class codes and volumes.  Returns a list of dicts
     ``lo, hi, part, code, vol`` (CPU tensors)."""
-    from fairify_amd.engine.bab import _pa_table
+    from fairify_amd.engine.search import pa_table
     from fairify_amd.ops import count as OC
 
     lo_np, hi_np = lo.numpy().astype(np.int64), hi.numpy().astype(np.int64)
-    values, pairs = _pa_table(q, lo_np, hi_np)
+    values, pairs = pa_table(q, lo_np, hi_np)
     vt, pt = torch.from_numpy(values), torch.from_numpy(pairs)
     free = OC.free_dims(q)
     score = OC.split_scores(be.mlp)

@@ -10,7 +10,7 @@ import torch
 
 import count_cases as cc
 import rate_cases as rc
-from fairify_amd.engine.bab import _pa_table
+from fairify_amd.engine.search import pa_table
 from fairify_amd.engine.count import _enumerate
 from fairify_amd.engine.rate import exact_flags
 from fairify_amd.models.mlp import random_mlp
@@ -32,7 +32,7 @@ def _net(name, k):
 
 
 def _tables(q, lo, hi, dev):
-    values, pairs = _pa_table(q, lo.numpy().astype(np.int64), hi.numpy().astype(np.int64))
+    values, pairs = pa_table(q, lo.numpy().astype(np.int64), hi.numpy().astype(np.int64))
     return torch.from_numpy(values).to(dev), torch.from_numpy(pairs).to(dev)
 
 

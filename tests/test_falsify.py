@@ -110,7 +110,7 @@ def test_fused_falsifier_matches_sim_and_is_sound(cuda, monkeypatch, model):
     * it decides at least 98 % of what the unfused path decides."""
     from fairify_amd import presets
     from fairify_amd.engine import falsify as F
-    from fairify_amd.engine.bab import _pa_table
+    from fairify_amd.engine.search import pa_table
     from fairify_amd.models.zoo import get_model
     from fairify_amd.ops import hip
     from fairify_amd.partition import processing_order
@@ -121,7 +121,7 @@ def test_fused_falsifier_matches_sim_and_is_sound(cuda, monkeypatch, model):
     lo_np, hi_np = grid.decode(ids)
     m = get_model(model, weights="random", seed=0)
     be = Backend(m, cuda)
-    v_np, p_np = _pa_table(q, lo_np, hi_np)
+    v_np, p_np = pa_table(q, lo_np, hi_np)
     values, pairs = torch.from_numpy(v_np).to(cuda), torch.from_numpy(p_np).to(cuda)
     lo, hi = torch.from_numpy(lo_np).to(cuda).float(), torch.from_numpy(hi_np).to(cuda).float()
     pids = torch.from_numpy(ids).to(cuda)
@@ -158,7 +158,7 @@ def test_fused_falsifier_relaxed_is_sound_and_matches_torch(cuda, monkeypatch, p
     exact network, and the kernel decides at least 95 % of what the PyTorch local search decides."""
     from fairify_amd import presets
     from fairify_amd.engine import falsify as F
-    from fairify_amd.engine.bab import _pa_table
+    from fairify_amd.engine.search import pa_table
     from fairify_amd.models.zoo import get_model
     from fairify_amd.partition import processing_order
 
@@ -169,7 +169,7 @@ def test_fused_falsifier_relaxed_is_sound_and_matches_torch(cuda, monkeypatch, p
     lo_np, hi_np = grid.decode(ids)
     m = get_model(model, weights="random", seed=0)
     be = Backend(m, cuda)
-    v_np, p_np = _pa_table(q, lo_np, hi_np)
+    v_np, p_np = pa_table(q, lo_np, hi_np)
     values, pairs = torch.from_numpy(v_np).to(cuda), torch.from_numpy(p_np).to(cuda)
     lo, hi = torch.from_numpy(lo_np).to(cuda).float(), torch.from_numpy(hi_np).to(cuda).float()
     pids = torch.from_numpy(ids).to(cuda)

@@ -49,9 +49,9 @@ def test_lpbab_matches_bruteforce(seed):
     lo, hi = grid.decode(ids)
     hi = np.minimum(hi, lo + 1)                  # <= 2 values per free dim: enumerable
     m = random_mlp(13, [6, 5], seed=seed, bias_scale=0.5)
-    from fairify_amd.engine.bab import _pa_table
+    from fairify_amd.engine.search import pa_table
 
-    values, pairs = _pa_table(q, lo[:1], hi[:1])
+    values, pairs = pa_table(q, lo[:1], hi[:1])
     pa = q.pa_idx[0]
     decided = 0
     for k in range(len(ids)):
@@ -180,7 +180,7 @@ def test_lp_model_runs_after_other_highs_users():
 def test_lpbab_multivalued_pa_with_sign_pretests(seed):
     """Race (5 values, 20 ordered pairs): the per-value single-copy sign tests that close whole
     rows / columns of the pair table keep the verdicts equal to brute force."""
-    from fairify_amd.engine.bab import _pa_table
+    from fairify_amd.engine.search import pa_table
     from fairify_amd.smt import lpbab
 
     pre = presets.get("src/AC-race")
@@ -192,7 +192,7 @@ def test_lpbab_multivalued_pa_with_sign_pretests(seed):
     hi = np.minimum(hi, lo + 1)
     hi[:, pa] = hi_full[:, pa]                     # all 5 race values, <= 2 values elsewhere
     m = random_mlp(13, [6, 5], seed=seed, bias_scale=0.5)
-    values, pairs = _pa_table(q, lo[:1], hi[:1])
+    values, pairs = pa_table(q, lo[:1], hi[:1])
     assert len(pairs) > 2
     for k in range(len(ids)):
         rb = _row_bounds(m, lo[k], hi[k], q, values)
@@ -224,7 +224,7 @@ def test_lpbab_relaxed_matches_bruteforce(seed, tau, race):
     """Relaxed queries (|x_r - x'_r| <= tau on RA = age, x' NOT clipped to the box; reference
     relaxed/BM/Verify-BM.py:53-54, utils/verif_utils.py:879-887): both orientations, x' bounds over
     the widened box; verdicts equal enumeration of every (x, x') pair."""
-    from fairify_amd.engine.bab import _pa_table
+    from fairify_amd.engine.search import pa_table
     from fairify_amd.smt import lpbab
     from fairify_amd.spec import ADULT, Query
 
@@ -240,7 +240,7 @@ def test_lpbab_relaxed_matches_bruteforce(seed, tau, race):
     m = random_mlp(13, [6, 5], seed=seed, bias_scale=0.5)
     decided = 0
     for k in range(len(ids)):
-        values, pairs = _pa_table(q, lo[k:k + 1], hi[k:k + 1])
+        values, pairs = pa_table(q, lo[k:k + 1], hi[k:k + 1])
         rb = _row_bounds(m, lo[k], hi[k], q, values)
         lw, hw = lo[k].copy(), hi[k].copy()
         lw[ra] -= tau

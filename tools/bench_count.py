@@ -58,7 +58,7 @@ def main():
 
     from fairify_amd import presets
     from fairify_amd.engine import count as EC
-    from fairify_amd.engine.bab import _pa_table
+    from fairify_amd.engine.search import pa_table
     from fairify_amd.models.zoo import get_model
     from fairify_amd.ops import count as OC
     from fairify_amd.ops import hip
@@ -119,7 +119,7 @@ def main():
         groups = EC.pa_groups(q, elo_np, ehi_np)
         keep = groups[0]                                                          # one PA table
         elo_np, ehi_np, ids_e = elo_np[keep], ehi_np[keep], ids_e[keep]
-        values, pairs = _pa_table(q, elo_np, ehi_np)
+        values, pairs = pa_table(q, elo_np, ehi_np)
         vt, pt = torch.from_numpy(values).to(dev), torch.from_numpy(pairs).to(dev)
         llo_np, lhi_np = shrink(elo_np, ehi_np, OC.free_dims(q), leaf)
         llo = torch.from_numpy(llo_np).to(dev, torch.float32)

@@ -28,7 +28,7 @@ def main():
     import torch
 
     from fairify_amd import presets
-    from fairify_amd.engine.bab import _pa_table
+    from fairify_amd.engine.search import pa_table
     from fairify_amd.models.zoo import get_model
     from fairify_amd.ops.backend import Backend
     from fairify_amd.partition import processing_order
@@ -43,7 +43,7 @@ def main():
     # random sub-boxes (what the BaB frontier looks like a few levels down)
     a = lo + np.floor(rng.random(lo.shape) * (hi - lo + 1) * 0.5).astype(lo.dtype)
     b = np.minimum(hi, a + np.floor(rng.random(lo.shape) * (hi - lo + 1) * 0.6).astype(lo.dtype))
-    values_np, pairs_np = _pa_table(q, lo, hi)
+    values_np, pairs_np = pa_table(q, lo, hi)
     values = torch.from_numpy(values_np).to(dev)
     pairs = torch.from_numpy(pairs_np).to(dev)
     pa = torch.tensor(list(q.pa_idx), device=dev)

@@ -187,7 +187,7 @@ def main():
     ap.add_argument("--summary-only", action="store_true")
     args = ap.parse_args()
     from fairify_amd import presets
-    from fairify_amd.engine.bab import _pa_table
+    from fairify_amd.engine.search import pa_table
     from fairify_amd.models.zoo import get_model
     from fairify_amd.ops.backend import Backend
     from fairify_amd.partition import processing_order
@@ -203,7 +203,7 @@ def main():
     m = get_model(args.model, weights=args.weights, seed=0)
     be = Backend(m, device="cpu")
     lo_np, hi_np = grid.decode(order)
-    values_np, pairs_np = _pa_table(q, lo_np, hi_np)
+    values_np, pairs_np = pa_table(q, lo_np, hi_np)
     values = torch.from_numpy(values_np)
     pairs = torch.from_numpy(pairs_np)
     pa = torch.tensor(list(q.pa_idx))

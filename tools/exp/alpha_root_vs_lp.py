@@ -5,7 +5,7 @@ import sys, numpy as np, torch
 import os; _R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, _R); sys.path.insert(0, os.path.join(_R, "tools", "exp"))
 from beta_proto import layer_bounds, pair_low
 from fairify_amd import presets
-from fairify_amd.engine.bab import _pa_table
+from fairify_amd.engine.search import pa_table
 from fairify_amd.models.zoo import get_model
 from fairify_amd.ops.backend import Backend
 from fairify_amd.ops import reference as ref
@@ -15,7 +15,7 @@ m = get_model("AC-7", weights="zoo", seed=0); be = Backend(m, "cpu")
 ws = [w.double() for w in be.ws]; bs = [b.double() for b in be.bs]
 NH = sum(int(w.shape[1]) for w in ws[:-1]); pa = list(q.pa_idx)
 ids = np.array([12596]); lo_all, hi_all = grid.decode(ids)
-vals, pairs = _pa_table(q, lo_all, hi_all)
+vals, pairs = pa_table(q, lo_all, hi_all)
 lbs, ubs = milp.layer_bounds_rows(be, lo_all, hi_all, q, vals, widen_ra=False)
 for vi, vj in pairs:
     rb = {v: ([lb[0, v] for lb in lbs], [ub[0, v] for ub in ubs]) for v in range(vals.shape[0])}

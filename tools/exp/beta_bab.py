@@ -144,7 +144,7 @@ def main():
     ap.add_argument("--verify", action="store_true")
     a = ap.parse_args()
     from fairify_amd import presets
-    from fairify_amd.engine.bab import _pa_table
+    from fairify_amd.engine.search import pa_table
     from fairify_amd.models.zoo import get_model
     from fairify_amd.ops.backend import Backend
     from fairify_amd.smt import milp
@@ -160,7 +160,7 @@ def main():
     pa = list(q.pa_idx)
     ids = np.array([int(x) for x in a.pids.split(",")])
     lo_all, hi_all = grid.decode(ids)
-    vals, pairs = _pa_table(q, lo_all, hi_all)
+    vals, pairs = pa_table(q, lo_all, hi_all)
     lbs, ubs = milp.layer_bounds_rows(be_, lo_all, hi_all, q, vals, widen_ra=False)
     for k, pid in enumerate(ids):
         t0 = time.time()

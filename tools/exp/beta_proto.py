@@ -125,7 +125,7 @@ def main():
     ap.add_argument("--no-beta", action="store_true")
     a = ap.parse_args()
     from fairify_amd import presets
-    from fairify_amd.engine.bab import _pa_table
+    from fairify_amd.engine.search import pa_table
     from fairify_amd.models.zoo import get_model
     from fairify_amd.ops.backend import Backend
 
@@ -141,7 +141,7 @@ def main():
     pa = list(q.pa_idx)
     ids = np.array([int(x) for x in a.pids.split(",")])
     lo_all, hi_all = grid.decode(ids)
-    vals, pairs = _pa_table(q, lo_all, hi_all)
+    vals, pairs = pa_table(q, lo_all, hi_all)
     for k, pid in enumerate(ids):
         t0 = time.time()
         verdict, nodes_tot = "unsat", 0

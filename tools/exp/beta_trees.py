@@ -29,8 +29,9 @@ def main():
 
     from fairify_amd import presets
     from fairify_amd.engine import exact
-    from fairify_amd.engine.bab import SAT, UNSAT, _pa_table
+    from fairify_amd.engine.bab import SAT, UNSAT
     from fairify_amd.engine.beta_bab import BetaBaBSolver, BetaConfig
+    from fairify_amd.engine.search import pa_table
     from fairify_amd.models.zoo import get_model
     from fairify_amd.ops.backend import Backend
     from fairify_amd.smt import lpbab, milp
@@ -41,7 +42,7 @@ def main():
     lo, hi = grid.decode(np.array([args.gid]))
     m = get_model(args.model, weights="zoo", seed=0)
     be = Backend(m, device="cpu")
-    values, pairs = _pa_table(q, lo, hi)
+    values, pairs = pa_table(q, lo, hi)
     Pp = pairs.shape[0]
     O = 2 if q.relaxed else 1
     lbs, ubs = milp.layer_bounds_rows(be, lo, hi, q, values, widen_ra=False)

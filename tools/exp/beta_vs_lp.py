@@ -33,8 +33,9 @@ def main():
     import torch
 
     from fairify_amd import presets
-    from fairify_amd.engine.bab import SAT, UNSAT, _pa_table
+    from fairify_amd.engine.bab import SAT, UNSAT
     from fairify_amd.engine.beta_bab import BetaBaBSolver, BetaConfig
+    from fairify_amd.engine.search import pa_table
     from fairify_amd.models.zoo import get_model
     from fairify_amd.ops.backend import Backend
     from fairify_amd.smt import lpbab
@@ -60,7 +61,7 @@ def main():
     name = {SAT: "sat", UNSAT: "unsat"}
     for i, gid in enumerate(ids):
         l1, h1 = lo[i:i + 1], hi[i:i + 1]
-        values_np, pairs_np = _pa_table(q, l1, h1)
+        values_np, pairs_np = pa_table(q, l1, h1)
         t0 = time.time()
         fut = lpbab.submit(be, m, q, l1, h1, values_np, pairs_np, args.lp_budget, 600.0, workers=1)
         v, _, lp_nodes = fut[0].result()

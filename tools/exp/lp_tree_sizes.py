@@ -45,9 +45,9 @@ def main():
     be = Backend(m, "cpu")
     ids = processing_order(grid, 0)[a.skip:a.skip + a.n]
     lo, hi = grid.decode(ids)
-    from fairify_amd.engine.bab import _pa_table
+    from fairify_amd.engine.search import pa_table
 
-    vals, pairs = _pa_table(q, lo, hi)
+    vals, pairs = pa_table(q, lo, hi)
     lbs, ubs = milp.layer_bounds_rows(be, lo, hi, q, vals, widen_ra=False)
     hist = collections.Counter()
     for k in range(len(lo)):

@@ -30,7 +30,7 @@ def main():
     import torch
 
     from fairify_amd import presets
-    from fairify_amd.engine.bab import _pa_table
+    from fairify_amd.engine.search import pa_table
     from fairify_amd.engine.sim import simulate
     from fairify_amd.models.zoo import get_model
     from fairify_amd.ops import hip as H
@@ -42,7 +42,7 @@ def main():
     grid, q = pre.grid(), pre.resolved()
     ids = processing_order(grid, 0)[:args.partitions]
     lo_np, hi_np = grid.decode(ids)
-    values_np, pairs_np = _pa_table(q, lo_np, hi_np)
+    values_np, pairs_np = pa_table(q, lo_np, hi_np)
     values = torch.from_numpy(values_np).to(dev)
     pairs = torch.from_numpy(pairs_np).to(dev)
     pids = torch.from_numpy(ids).to(dev)
