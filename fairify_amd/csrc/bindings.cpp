@@ -580,6 +580,15 @@ PYBIND11_MODULE(_C, m) {
     a.cand_x = k.need<float>("cand_x"); a.cand_xp = k.need<float>("cand_xp");
     a.cand_v = k.need<int64_t>("cand_v"); a.cand_o = k.need<int64_t>("cand_o");
     a.scores = k.ptr<float>("scores"); a.leaf = k.ptr<uint8_t>("leaf");
+    // the fields the native BaB runtime sets (absent: 0 / nullptr)
+    a.skip_closed = k.i("skip_closed", 0);
+    a.status = k.ptr<const int8_t>("status"); a.part = k.ptr<const int>("part");
+    a.smear = k.i("smear", 0);
+    a.lay_lb = k.ptr<const float>("lay_lb"); a.lay_ub = k.ptr<const float>("lay_ub"); a.lay_N = k.i("lay_N", 0);
+    a.W0T = k.ptr<const float>("W0T"); a.n1 = k.i("n1", 0);
+    if ((a.status == nullptr) != (a.part == nullptr)) throw std::invalid_argument("certify: status and part go together");
+    if (a.smear && (!a.lay_lb || !a.lay_ub || !a.W0T || a.n1 <= 0 || a.lay_N < a.n1))
+      throw std::invalid_argument("certify: smear needs lay_lb, lay_ub, W0T and 0 < n1 <= lay_N");
     ckl(fa_certify_launch(a, finish(k)), "certify");
   });
 

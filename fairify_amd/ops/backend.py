@@ -258,7 +258,8 @@ class Backend:
 
     # ----------------------------------------------------------------------------- BaB node test
     def pair_certify(self, res_x, res_xp, xlo, xhi, xplo, xphi, pairs, values, pa, shared, relaxed):
-        if self.hip:
+        # the kernels hold a node's dims in registers (n0 <= 32); wider inputs take the reference on the device
+        if self.hip and xlo.shape[1] <= 32:
             from . import hip
 
             return hip.pair_certify(self, res_x, res_xp, xlo, xhi, xplo, xphi, pairs, values, pa, shared, relaxed)

@@ -347,13 +347,60 @@ def crown_phase(be, lo: torch.Tensor, hi: torch.Tensor, res: ref.BoundResult, ph
 
 
 # ------------------------------------------------------------------------------------------------
-def pair_certify(be, res_x, res_xp, xlo, xhi, xplo, xphi, pairs, values, pa, shared, relaxed) -> ref.PairDecision:
+def smear_w0t(W0: torch.Tensor) -> torch.Tensor:
+    """``CertArgs.W0T`` of first-layer weights ``W0`` [n0, n1]: [n1, NM] rows of ``|W0[:, j]|``, zero
+    padded to the certify kernel's register width (NM = 16 for n0 <= 16, else 32)."""
+    n0, n1 = W0.shape
+    if n0 > 32:
+        raise ValueError("smear scores need n0 <= 32")
+    out = torch.zeros(n1, 16 if n0 <= 16 else 32, dtype=torch.float32, device=W0.device)
+    out[:, :n0] = W0.to(torch.float32).abs().T
+    return out
+
+
+def pair_certify(be, res_x, res_xp, xlo, xhi, xplo, xphi, pairs, values, pa, shared, relaxed, *, ra=(), tau=0.0,
+                 skip_closed=False, status=None, part=None, smear=False, lay_lb=None, lay_ub=None, W0T=None,
+                 prefill=None, full=False):
+    """The pair certificate of ``Nn`` nodes (csrc/certify.hip) -> ref.PairDecision.
+
+    The keyword-only arguments are the ``CertArgs`` fields the native BaB runtime sets; the defaults
+    are the torch loop's call.  ``ra`` / ``tau``: the candidate x' is clipped to within tau of x on
+    these dims.  ``status`` [P] int8 with ``part`` [Nn] int32: nodes of partitions that are not
+    RUNNING / STOPPING are closed unevaluated.  ``skip_closed``: closed nodes write only open, score
+    and leaf.  ``smear`` with ``lay_lb`` / ``lay_ub`` [Nn*V, lay_N] (layer 0 first) and ``W0T``
+    (:func:`smear_w0t`): first-layer smear split scores.  ``prefill``: the outputs start filled with
+    this value (what a skipped node leaves behind).  ``full``: also return a dict with ``gmin`` and
+    ``tstar`` [Nn, Q] (written by the two-kernel path only), ``scores`` [Nn, 2 n0], ``leaf`` and the
+    uint8 open flags ``open_u8``."""
     Nn, n0 = xlo.shape
     dev = xlo.device
     V = values.shape[0]
     Pp = pairs.shape[0]
     norient = 2 if relaxed else 1
-    f32 = dict(dtype=torch.float32, device=dev)
+    ra = [int(i) for i in ra]
+    if any(not 0 <= i < n0 for i in ra):
+        raise ValueError("ra dim out of range")
+    extra = {}
+    if (status is None) != (part is None):
+        raise ValueError("status and part go together")
+    if status is not None:
+        status = _c(status, torch.int8, None, "status")
+        part = _c(part, torch.int32, (Nn,), "part")
+        if status.dim() != 1 or (Nn and not 0 <= int(part.min()) <= int(part.max()) < status.shape[0]):
+            raise ValueError("part indexes status [P]")
+        extra.update(_ptrs(status=status, part=part))
+    if skip_closed:
+        extra["skip_closed"] = 1
+    if smear:
+        if lay_lb is None or lay_ub is None or W0T is None or lay_lb.dim() != 2:
+            raise ValueError("smear needs lay_lb, lay_ub and W0T")
+        lay_N, n1 = lay_lb.shape[1], W0T.shape[0]
+        lay_lb = _c(lay_lb, torch.float32, (Nn * V, lay_N), "lay_lb")
+        lay_ub = _c(lay_ub, torch.float32, (Nn * V, lay_N), "lay_ub")
+        W0T = _c(W0T, torch.float32, (n1, 16 if n0 <= 16 else 32), "W0T")
+        if not 0 < n1 <= lay_N:
+            raise ValueError("smear: the first layer's n1 neurons lead the lay_N layer bounds")
+        extra.update(_ptrs(lay_lb=lay_lb, lay_ub=lay_ub, W0T=W0T), smear=1, lay_N=lay_N, n1=n1)
     xlo = _c(xlo, torch.float32, (Nn, n0), "xlo")
     xhi = _c(xhi, torch.float32, (Nn, n0), "xhi")
     xplo = _c(xplo, torch.float32, (Nn, n0), "xplo")
@@ -365,31 +412,42 @@ def pair_certify(be, res_x, res_xp, xlo, xhi, xplo, xphi, pairs, values, pa, sha
     values_c = _c(values, torch.int64, None, "values")
     sh = _c(shared, torch.uint8, (n0,), "shared")
     Q = Pp * norient
-    gmin = torch.empty(Nn, Q, **f32)
-    tstar = torch.empty(Nn, Q, **f32)
-    open_ = torch.empty(Nn, dtype=torch.uint8, device=dev)
-    score = torch.empty(Nn, **f32)
-    split = torch.empty(Nn, dtype=torch.int64, device=dev)
-    cx = torch.empty(Nn, n0, **f32)
-    cxp = torch.empty(Nn, n0, **f32)
-    cv = torch.empty(Nn, dtype=torch.int64, device=dev)
-    co = torch.empty(Nn, dtype=torch.int64, device=dev)
+
+    def new(*shape, dtype=torch.float32):
+        t = torch.empty(*shape, dtype=dtype, device=dev)
+        return t if prefill is None else t.fill_(prefill)
+
+    gmin = new(Nn, Q)
+    tstar = new(Nn, Q)
+    open_ = new(Nn, dtype=torch.uint8)
+    score = new(Nn)
+    split = new(Nn, dtype=torch.int64)
+    cx = new(Nn, n0)
+    cxp = new(Nn, n0)
+    cv = new(Nn, dtype=torch.int64)
+    co = new(Nn, dtype=torch.int64)
     # the forms and logit bounds of the x rows, and (key + "p") of the x' rows
     forms = {}
     for r, p in ((res_x, ""), (res_xp, "p")):
         for key, t in (("Lc", r.Lc), ("L0", r.L0), ("Le", r.Le), ("Uc", r.Uc), ("U0", r.U0), ("Ue", r.Ue),
                        ("olb", r.out_lb), ("oub", r.out_ub)):
             forms[key + p] = _c(t, torch.float32)
-    scores = torch.empty(Nn, 2 * n0, **f32)
-    leaf = torch.empty(Nn, dtype=torch.uint8, device=dev)
+    scores = new(Nn, 2 * n0)
+    leaf = new(Nn, dtype=torch.uint8)
     if Nn:
-        ext().certify(Nn=Nn, n0=n0, V=V, Pp=Pp, norient=norient, pa=[int(i) for i in pa.tolist()], ra=[], tau=0.0,
-                      unit=be.unit, gmarg=ref.gamma(2 * n0 + 4, be.unit), stream=_stream(dev),
+        pa_l = [int(i) for i in pa.tolist()]
+        if any(not 0 <= i < n0 for i in pa_l) or tuple(values_c.shape) != (V, len(pa_l)):
+            raise ValueError("pa dims out of range or values not [V, npa]")
+        ext().certify(Nn=Nn, n0=n0, V=V, Pp=Pp, norient=norient, pa=pa_l, ra=ra,
+                      tau=float(tau), unit=be.unit, gmarg=ref.gamma(2 * n0 + 4, be.unit), stream=_stream(dev), **extra,
                       **_ptrs(xlo=xlo, xhi=xhi, xplo=xplo, xphi=xphi, pairs=pairs_c, values=values_c, shared=sh,
                               gmin=gmin, tstar=tstar, open=open_, score=score, split_dim=split, cand_x=cx,
                               cand_xp=cxp, cand_v=cv, cand_o=co, scores=scores, leaf=leaf, **forms))
-    return ref.PairDecision(open_=open_.bool(), score=score, split_dim=split, cand_x=cx, cand_xp=cxp,
-                            cand_v=cv, cand_orient=co)
+    dec = ref.PairDecision(open_=open_.bool(), score=score, split_dim=split, cand_x=cx, cand_xp=cxp,
+                           cand_v=cv, cand_orient=co)
+    if full:
+        return dec, dict(gmin=gmin, tstar=tstar, scores=scores, leaf=leaf, open_u8=open_)
+    return dec
 
 
 # ------------------------------------------------------------------------------------------------

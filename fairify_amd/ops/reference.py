@@ -823,6 +823,8 @@ def pair_certify(res_x: BoundResult, res_xp: BoundResult, xlo: torch.Tensor, xhi
         else:
             imp = (oub_x[:, vi] <= 0) | (olb_p[:, vj] >= 0)
         gmin = torch.where(imp, torch.full_like(gmin, -1.0), gmin)
+        # a non-finite certificate value never closes a node (csrc/certify.hip: NaN counts as +inf)
+        gmin = torch.where(gmin.isnan(), torch.full_like(gmin, math.inf), gmin)
         gbest, pbest = gmin.max(dim=-1)                                # [Nn]
         upd = gbest > best_g
         tstar = torch.gather(ts, 2, targ[:, :, None])[..., 0]          # [Nn, P]
