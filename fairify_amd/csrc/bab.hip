@@ -29,6 +29,7 @@
 #include <algorithm>
 
 #include "args.h"
+#include "wave.h"
 
 #define ST_UNKNOWN 0
 #define ST_SAT 1
@@ -75,27 +76,6 @@ struct FaPackedDims {
   unsigned long long v;
   __device__ __forceinline__ int operator[](int j) const { return (int)((v >> (7 * j)) & 127ull); }
 };
-
-// (score, dim) arg-max over the wave: larger score wins, ties go to the lower dimension (the
-// sequential scan's first strict maximum)
-__device__ __forceinline__ void fa_wave_argmax(float& s, int& d) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float s2 = __shfl_xor(s, o);
-    const int d2 = __shfl_xor(d, o);
-    if (s2 > s || (s2 == s && d2 < d)) { s = s2; d = d2; }
-  }
-}
-
-// the same arg-max over the lane's 16-lane group (xor offsets below 16 stay inside the group)
-__device__ __forceinline__ void fa_group_argmax(float& s, int& d) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) {
-    const float s2 = __shfl_xor(s, o);
-    const int d2 = __shfl_xor(d, o);
-    if (s2 > s || (s2 == s && d2 < d)) { s = s2; d = d2; }
-  }
-}
 
 __device__ __forceinline__ void fa_settle_counters(const SettleArgs& s) {
   // level counters straight into pinned host memory (no blit per level), next slot cleared; the
@@ -149,16 +129,6 @@ __device__ __forceinline__ bool fa_leaf_poss(const SplitArgs& a, int n, int t) {
   const int o = t / a.Pp, q = t - o * a.Pp;
   const size_t ri = (size_t)n * a.V + (int)a.pairs[2 * q], rj = (size_t)n * a.V + (int)a.pairs[2 * q + 1];
   return (o == 0) ? (a.olb[ri] < 0.f && a.oubp[rj] > 0.f) : (a.oub[ri] > 0.f && a.olbp[rj] < 0.f);
-}
-
-// Inclusive wave64 prefix sum.
-__device__ __forceinline__ int fa_wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o);
-    if (lane >= o) v += u;
-  }
-  return v;
 }
 
 // One wave64 per node, npw (1..FA_SPLIT_NPW) nodes per wave, FA_SPLIT_WAVES * npw nodes per
@@ -408,7 +378,7 @@ __global__ void __launch_bounds__(64 * FA_SPLIT_WAVES) fa_split_kernel(SplitArgs
         float sv = s0v >= s1v ? s0v : s1v;                 // ties: d0 < d1
         int d = s0v >= s1v ? d0 : d1;
         if (sv <= -0.5f) d = 0x7fffffff;
-        fa_wave_argmax(sv, d);
+        fa_group_argmax<64>(sv, d);
         if (sv <= -0.5f) break;                            // wave-uniform after the reduction
         dims[m++] = d;
         if (d == d0) s0v = -1.f;
@@ -541,7 +511,7 @@ __global__ void __launch_bounds__(64 * FA_SPLIT_WAVES) fa_split_group_kernel(Spl
       float sv = s0v >= s1v ? s0v : s1v;                    // ties: d0 < d1
       int d = s0v >= s1v ? d0 : d1;
       if (sv <= -0.5f) d = 0x7fffffff;
-      fa_group_argmax(sv, d);
+      fa_group_argmax<16>(sv, d);
       more = more && j < mreq && sv > -0.5f;                // once false it stays false: m == j here
       if (more) {
         pl.dims |= (unsigned long long)d << (7 * j);

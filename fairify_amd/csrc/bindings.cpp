@@ -31,6 +31,9 @@ extern "C" int fa_point_try_launch(const NetDesc& net, BoundArgs a, hipStream_t 
 extern "C" int fa_forward_launch(const NetDesc& net, FwdArgs a, hipStream_t stream);
 extern "C" int fa_sim_launch(const NetDesc& net, SimArgs a, hipStream_t stream);
 extern "C" int fa_sim_shaped(const NetDesc& net);
+extern "C" int fa_sym_shaped(const NetDesc& net, unsigned long long fold_mask);
+extern "C" int fa_crown_shaped(const NetDesc& net, int mask);
+extern "C" int fa_refine_shaped(const NetDesc& net, int logit);
 extern "C" int fa_rate_launch(const NetDesc& net, RateArgs a, hipStream_t stream);
 extern "C" int fa_count_enum_launch(const NetDesc& net, EnumArgs a, hipStream_t stream);
 extern "C" int fa_count_rows_launch(CountArgs a, hipStream_t stream);
@@ -393,6 +396,12 @@ PYBIND11_MODULE(_C, m) {
     ckl(fa_sim_launch(net.d, a, finish(k)), "sim");
   });
   m.def("sim_shaped", [](const Net& net) { return fa_sim_shaped(net.d) != 0; });
+  // would a launch run a compile-time-shape instance?  The launch's own selection (the *_SHAPED
+  // switches included): symbolic by fold mask, crown with / without a forced-dead mask, refine
+  // without / with the logit's backward pass (refine / refine_crown and backward_bounds)
+  m.def("sym_shaped", [](const Net& net, unsigned long long fold) { return fa_sym_shaped(net.d, fold) != 0; });
+  m.def("crown_shaped", [](const Net& net, bool mask) { return fa_crown_shaped(net.d, mask) != 0; });
+  m.def("refine_shaped", [](const Net& net, bool logit) { return fa_refine_shaped(net.d, logit) != 0; });
 
   // discrimination-rate counts (csrc/rate.hip); flips / amb zero-initialised by the caller
   m.def("rate", [](const Net& net, py::kwargs kw) {

@@ -13,6 +13,7 @@
 
 #include "pointfwd.h"
 #include "regfwd.h"
+#include "wave.h"
 
 // ---- leaf enumeration ------------------------------------------------------------------------
 // A workgroup walks the leaves blockIdx.x, blockIdx.x + gridDim.x, ...: W is staged once for many
@@ -258,15 +259,6 @@ extern "C" int fa_count_rows_launch(CountArgs a, hipStream_t stream) {
 }
 
 // ---- level step ------------------------------------------------------------------------------
-__device__ __forceinline__ int fa_count_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-
 // One node per lane.  FAIR / UNFAIR nodes add their volume to their partition; an OPEN node of at
 // most leaf_points points goes to the leaf list, any other OPEN node is halved along the dim with
 // the largest (hi_d - lo_d) * s_d (fp32 product, lowest d on ties) into the child pool.
@@ -312,7 +304,7 @@ __global__ void __launch_bounds__(FA_THREADS) fa_count_level_kernel(CountArgs a)
     else nchild = 2;
   }
   // one atomic per wave and list
-  const int ci = fa_count_incl_scan(nchild, lane), li = fa_count_incl_scan(nleaf, lane);
+  const int ci = fa_wave_incl_scan(nchild, lane), li = fa_wave_incl_scan(nleaf, lane);
   int cb = 0, lb = 0;
   if (lane == 63) {
     if (ci) cb = atomicAdd(&a.counters[0], ci);

@@ -24,30 +24,12 @@
 // form's error term -- so sigma * y >= lambda . x + c - err holds for the exact network.
 #include <hip/hip_runtime.h>
 
-#include <stdlib.h>
-
-#include <algorithm>
-#include <map>
-#include <mutex>
-
 #include "args.h"
+#include "launch.h"
+#include "wave.h"
 
 #define FA_CROWN_MAXW 256
 #define FA_CROWN_WAVES 4
-
-__device__ __forceinline__ float fa_gam(int k, float u) {
-#pragma clang fp contract(off)   // (k + 2) u and 4 u are exact: fused or not, the same value
-  const float ku = (float)(k + 2) * u;
-  return ku / (1.f - ku) * (1.f + 4.f * u);
-}
-
-// butterfly sum within aligned groups of G lanes (every lane of the group gets the total)
-template <int G>
-__device__ __forceinline__ float fa_group_sum(float v) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // G lanes per box-row (G >= widest layer, up to 64): tiny networks (AC-8's 5-wide layers) pack
 // 64 / G rows into one wave instead of leaving 59 of 64 lanes idle.  WP = per-row slab stride.
@@ -462,7 +444,7 @@ __device__ __forceinline__ void fa_crown_layers_c(std::integer_sequence<int, IS.
 #ifndef FA_CROWN_WPE7
 #define FA_CROWN_WPE7 2
 #endif
-// S = FaShape<...>: the network's shape at compile time (crown_mfma_try picks the instance whose
+// S = FaShape<...>: the network's shape at compile time (pick_crown picks the instance whose
 // dims equal NetDesc's and whose unit roundoff is fp32's): the layer loop is unrolled per layer,
 // multiplier tiles exist only where the layer has neurons, and each row's input box is read once
 // into registers with the PA value substituted (not in the 7-tile instances: holding the box across
@@ -653,117 +635,84 @@ __attribute__((amdgpu_waves_per_eu(TM == 4 ? FA_CROWN_WPE4 : (TM == 7 ? FA_CROWN
 
 namespace {
 typedef void (*CrownMfmaKernel)(NetDesc, BoundArgs, CrownCfg);
-CrownMfmaKernel select_crown_mfma(int TM, bool mask) {
-  if (TM <= 1) return mask ? fa_crown_mfma_kernel<1> : fa_crown_mfma_kernel<1, FaShapeAny, false>;
-  if (TM <= 2) return mask ? fa_crown_mfma_kernel<2> : fa_crown_mfma_kernel<2, FaShapeAny, false>;
-  if (TM <= 4) return mask ? fa_crown_mfma_kernel<4> : fa_crown_mfma_kernel<4, FaShapeAny, false>;
-  if (TM <= 7) return mask ? fa_crown_mfma_kernel<7> : fa_crown_mfma_kernel<7, FaShapeAny, false>;
-  return nullptr;
-}
 
-// Compile-time shapes (common.h FaShape), each in the TM bucket select_crown_mfma picks for it: the
-// wide crown models of the bench, then the zoo's one-tile chains.  FAIRIFY_CROWN_SHAPED=0 (read per
-// launch: the bitwise-equality test toggles it) keeps the run-time-shape kernels.
-struct ShapedCrown {
-  int tm;
-  std::vector<int> dims;
-  CrownMfmaKernel k[2];   // without / with a forced-dead mask
+// the run-time-shape instances, one per TM bucket (launch.h fa_tm_bucket), with and without a mask
+#define FA_CROWN_TMS(X) X(1) X(2) X(4) X(7)
+
+// Compile-time shapes (common.h FaShape) as X(TM bucket, widths...), each in the bucket the
+// run-time-shape selection picks for it: the wide crown models of the bench, then the zoo's one-tile
+// chains.  A new shape is one line here: the selection table and the LDS registry both come from it.
+#define FA_CROWN_SHAPES(X)                                                                    \
+  X(7, 13, 100, 100, 1)   /* AC-4 */                                                          \
+  X(7, 13, 100, 1)        /* AC-2 */                                                          \
+  X(4, 13, 64, 64, 1)     /* AC-5 */                                                          \
+  X(4, 13, 50, 1)         /* AC-3 */                                                          \
+  X(1, 13, 5, 5, 1)       /* AC-8 */                                                          \
+  X(1, 13, 16, 8, 1)      /* AC-1 */                                                          \
+  X(1, 13, 12, 12, 1)     /* AC-6 */                                                          \
+  X(1, 13, 3, 3, 3, 3, 1) /* AC-9 */
+
+struct CrownPick {
+  CrownMfmaKernel k;   // nullptr: shape not supported by the MFMA variant
+  bool shaped;
 };
-template <int TM, int... D>
-ShapedCrown shaped_crown() {
-  return {TM, {D...}, {fa_crown_mfma_kernel<TM, FaShape<D...>, false>, fa_crown_mfma_kernel<TM, FaShape<D...>, true>}};
-}
 
-CrownMfmaKernel select_crown_shaped(const NetDesc& net, int TM, bool mask) {
-  const char* e = getenv("FAIRIFY_CROWN_SHAPED");
-  if (e && *e == '0') return nullptr;
-  if (net.unit != 0x1p-24f) return nullptr;   // the shaped instances fold fp32's gamma terms
-  static const std::vector<ShapedCrown> v = {
-      shaped_crown<7, 13, 100, 100, 1>(),        // AC-4
-      shaped_crown<7, 13, 100, 1>(),             // AC-2
-      shaped_crown<4, 13, 64, 64, 1>(),          // AC-5
-      shaped_crown<4, 13, 50, 1>(),              // AC-3
-      shaped_crown<1, 13, 5, 5, 1>(),            // AC-8
-      shaped_crown<1, 13, 16, 8, 1>(),           // AC-1
-      shaped_crown<1, 13, 12, 12, 1>(),          // AC-6
-      shaped_crown<1, 13, 3, 3, 3, 3, 1>(),      // AC-9
-  };
-  const int tmb = TM <= 1 ? 1 : TM <= 2 ? 2 : TM <= 4 ? 4 : 7;
-  for (const auto& s : v) {
-    if (s.tm != tmb || (int)s.dims.size() != net.n_layers + 1) continue;
-    bool same = true;
-    for (int l = 0; l <= net.n_layers && same; ++l) same = s.dims[l] == net.dims[l];
-    if (same) return s.k[mask ? 1 : 0];
-  }
-  return nullptr;
-}
-
-int crown_cus() {
-  static int cus = 0;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  });
-  return cus;
-}
-
-// 1 launched, 0 shape not supported by the MFMA variant, < 0 error
-int crown_mfma_try(const NetDesc& net, const BoundArgs& a, hipStream_t stream) {
+// The kernel a launch runs for this network (mask: with a forced-dead mask), for crown_mfma_try and
+// the fa_crown_shaped query alike.  FAIRIFY_CROWN_SHAPED=0 (read per launch: the bitwise-equality
+// test toggles it) keeps the run-time-shape kernels.
+CrownPick pick_crown(const NetDesc& net, bool mask) {
   static const bool off = [] {
     const char* e = getenv("FAIRIFY_CROWN_MFMA");
     return e && e[0] == '0';
   }();
-  if (off) return 0;
-  int TM = 1;
-  for (int l = 0; l <= net.n_layers; ++l) TM = std::max(TM, (net.dims[l] + 15) / 16);
-  const bool mask = a.dead_in || a.dead_part;
-  CrownMfmaKernel k = select_crown_mfma(TM, mask);
-  if (!k) return 0;
-  if (const CrownMfmaKernel ks = select_crown_shaped(net, TM, mask)) k = ks;
-  CrownCfg cfg{};
-  int offs = 0;
-  for (int l = 0; l < net.n_layers; ++l) {
-    cfg.w_lds[l] = offs;
-    offs += ((net.dims[l] + 15) / 16) * ((net.dims[l + 1] + 15) / 16) * 256;
+  if (off) return {nullptr, false};
+  const int tmb = fa_tm_bucket(fa_widest_tiles(net, 0, net.n_layers));
+  // the shaped instances fold fp32's gamma terms
+  if (!fa_env_off("FAIRIFY_CROWN_SHAPED") && net.unit == 0x1p-24f) {
+#define FA_CROWN_ENTRY(TM, ...)                                                      \
+  {2 * TM, {__VA_ARGS__}, fa_crown_mfma_kernel<TM, FaShape<__VA_ARGS__>, false>},  \
+      {2 * TM + 1, {__VA_ARGS__}, fa_crown_mfma_kernel<TM, FaShape<__VA_ARGS__>, true>},
+    static const std::vector<FaShaped<CrownMfmaKernel>> v = {FA_CROWN_SHAPES(FA_CROWN_ENTRY)};
+#undef FA_CROWN_ENTRY
+    if (const CrownMfmaKernel ks = fa_find_shaped(v, net, 2 * tmb + (mask ? 1 : 0))) return {ks, true};
   }
+  switch (tmb) {
+#define FA_CROWN_CASE(T) \
+  case T: return {mask ? fa_crown_mfma_kernel<T> : fa_crown_mfma_kernel<T, FaShapeAny, false>, false};
+    FA_CROWN_TMS(FA_CROWN_CASE)
+#undef FA_CROWN_CASE
+    default: return {nullptr, false};
+  }
+}
+
+// 1 launched, 0 shape not supported by the MFMA variant, < 0 error
+int crown_mfma_try(const NetDesc& net, const BoundArgs& a, hipStream_t stream) {
+  const CrownMfmaKernel k = pick_crown(net, a.dead_in || a.dead_part).k;
+  if (!k) return 0;
+  CrownCfg cfg{};
+  int offs = fa_lay_weights(net, net.n_layers, cfg.w_lds, 0);
   cfg.wfloats = offs;
   // the pre-permuted backward block (ops/backend.py:mfma_back_block) has this very layout; a
   // mismatch keeps the per-element gather
   cfg.wcopy = net.wback_floats == offs && (net.wback_off & 3) == 0;
-  for (int l = 0; l < net.n_layers; ++l) {
-    cfg.b_lds[l] = offs;
-    offs += net.dims[l + 1];
-  }
+  offs = fa_lay_biases(net, net.n_layers, cfg.b_lds, offs);
   cfg.floats = (offs + 3) & ~3;
   const size_t bytes = (size_t)cfg.floats * sizeof(float);
   if (bytes > 150 * 1024) return 0;
-  static std::mutex mu;
-  static std::map<std::pair<const void*, size_t>, int> occ;
-  int per_cu = 0;
-  {
-    std::lock_guard<std::mutex> g(mu);
-    const auto key = std::make_pair((const void*)k, bytes);
-    auto it = occ.find(key);
-    if (it == occ.end()) {
-      if (!fa_lds_ok(bytes)) return -4;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, bytes) != hipSuccess || per_cu <= 0) per_cu = 1;
-      occ[key] = per_cu;
-    } else {
-      per_cu = it->second;
-    }
-  }
+  const int per_cu = fa_blocks_per_cu((const void*)k, 256, bytes);
+  if (!per_cu) return -4;
   const long long tiles = (a.R + 15) / 16;
   long long blocks = (tiles + 3) / 4;
-  const long long cap = (long long)crown_cus() * per_cu;
+  const long long cap = (long long)fa_device_cus() * per_cu;
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), bytes, stream, net, a, cfg);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 1 : -(int)e;
 }
 }  // namespace
+
+// does a launch for this network (mask: with a forced-dead mask) run a compile-time-shape instance?
+extern "C" int fa_crown_shaped(const NetDesc& net, int mask) { return pick_crown(net, mask != 0).shaped; }
 
 // 0 on success; -1 if the network does not fit (a layer wider than FA_CROWN_MAXW or weights
 // beyond the LDS budget) -- callers then keep the forward forms.
@@ -798,14 +747,13 @@ extern "C" int fa_crown_launch(const NetDesc& net, BoundArgs a, hipStream_t stre
   return (int)hipGetLastError();
 }
 
-FA_LDS_REGISTER(FA_LDS_K(fa_crown_mfma_kernel<1>), FA_LDS_K(fa_crown_mfma_kernel<2>), FA_LDS_K(fa_crown_mfma_kernel<4>),
-                FA_LDS_K(fa_crown_mfma_kernel<7>), FA_LDS_K(fa_crown_kernel<4>), FA_LDS_K(fa_crown_kernel<8>),
-                FA_LDS_K(fa_crown_kernel<16>), FA_LDS_K(fa_crown_kernel<32>), FA_LDS_K(fa_crown_kernel<64>));
+FA_LDS_REGISTER(FA_LDS_K(fa_crown_kernel<4>), FA_LDS_K(fa_crown_kernel<8>), FA_LDS_K(fa_crown_kernel<16>),
+                FA_LDS_K(fa_crown_kernel<32>), FA_LDS_K(fa_crown_kernel<64>));
 #define FA_CROWN_LDS(TM, ...)                                         \
   FA_LDS_K((fa_crown_mfma_kernel<TM, FaShape<__VA_ARGS__>, true>)), \
-      FA_LDS_K((fa_crown_mfma_kernel<TM, FaShape<__VA_ARGS__>, false>))
-FA_LDS_REGISTER(FA_LDS_K((fa_crown_mfma_kernel<1, FaShapeAny, false>)), FA_LDS_K((fa_crown_mfma_kernel<2, FaShapeAny, false>)),
-                FA_LDS_K((fa_crown_mfma_kernel<4, FaShapeAny, false>)), FA_LDS_K((fa_crown_mfma_kernel<7, FaShapeAny, false>)));
-FA_LDS_REGISTER(FA_CROWN_LDS(7, 13, 100, 100, 1), FA_CROWN_LDS(7, 13, 100, 1), FA_CROWN_LDS(4, 13, 64, 64, 1),
-                FA_CROWN_LDS(4, 13, 50, 1), FA_CROWN_LDS(1, 13, 5, 5, 1),
-                FA_CROWN_LDS(1, 13, 16, 8, 1), FA_CROWN_LDS(1, 13, 12, 12, 1), FA_CROWN_LDS(1, 13, 3, 3, 3, 3, 1));
+      FA_LDS_K((fa_crown_mfma_kernel<TM, FaShape<__VA_ARGS__>, false>)),
+#define FA_CROWN_TM_LDS(T) FA_LDS_K(fa_crown_mfma_kernel<T>), FA_LDS_K((fa_crown_mfma_kernel<T, FaShapeAny, false>)),
+FA_LDS_REGISTER(FA_CROWN_TMS(FA_CROWN_TM_LDS));
+FA_LDS_REGISTER(FA_CROWN_SHAPES(FA_CROWN_LDS));
+#undef FA_CROWN_TM_LDS
+#undef FA_CROWN_LDS

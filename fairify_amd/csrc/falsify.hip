@@ -28,6 +28,7 @@
 #include <climits>
 
 #include "regfwd.h"
+#include "wave.h"
 
 namespace {
 
@@ -74,11 +75,6 @@ __host__ __device__ inline FalsifyLds fa_falsify_lds(const FalsifyArgs& a, int n
   return L;
 }
 
-__device__ __forceinline__ float fa_coord(uint32_t seed, int64_t pid, int s, int d, float lo, float hi) {
-  const uint32_t h = fa_rng(seed, pid, s, d);
-  return lo + (float)(h % ((uint32_t)(hi - lo) + 1u));
-}
-
 // PA dim d -> index into the PA list, or -1
 __device__ __forceinline__ int fa_pa_slot(const FalsifyArgs& a, int d) {
   int r = -1;
@@ -120,17 +116,6 @@ __device__ __forceinline__ float fa_pair_margin(const FalsifyArgs& a, const floa
   return g;
 }
 
-// wave-wide (value, index) selection: the largest value (sign = +1) or the smallest (sign = -1),
-// ties to the lower index; every lane returns the winner
-__device__ __forceinline__ void fa_wave_pick(float& v, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v2 = __shfl_xor(v, o);
-    const int i2 = __shfl_xor(i, o);
-    if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-  }
-}
-
 // Wave 0 selects the k extreme entries of buf[0..n) (sign +1: largest first, -1: smallest
 // first) into out[0..k); entries are masked while selecting and restored afterwards.
 __device__ void fa_select_extremes(float* buf, int n, int k, float sign, int* out, float* saved, int lane) {
@@ -141,7 +126,7 @@ __device__ void fa_select_extremes(float* buf, int n, int k, float sign, int* ou
       const float v = sign * buf[s];
       if (v > bv || (v == bv && s < bi)) { bv = v; bi = s; }
     }
-    fa_wave_pick(bv, bi);
+    fa_group_argmax<64>(bv, bi);
     if (lane == 0) {
       out[j] = bi;
       saved[j] = buf[bi];
@@ -196,7 +181,7 @@ __global__ void __launch_bounds__(FA_THREADS) fa_falsify_kernel(NetDesc net, Fal
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int k = 16 * t + 4 * grp + i;
-        Xb[t][i] = (k < n0 && sv) ? fa_coord(a.seed, pid, s, k, s_lo[k], s_hi[k]) : 0.f;
+        Xb[t][i] = (k < n0 && sv) ? fa_sample_coord(a.seed, pid, s, k, s_lo[k], s_hi[k]) : 0.f;
       }
     for (int v2 = 0; v2 < RV; ++v2) {
       const int v = v2 < V ? v2 : v2 - V;
@@ -236,7 +221,7 @@ __global__ void __launch_bounds__(FA_THREADS) fa_falsify_kernel(NetDesc net, Fal
     const int s = key / Pp, q = key % Pp;
     const int vi = (int)a.pairs[2 * q], vj = (int)a.pairs[2 * q + 1];
     for (int d = tid; d < n0; d += FA_THREADS) {
-      const float base = fa_coord(a.seed, pid, s, d, s_lo[d], s_hi[d]);
+      const float base = fa_sample_coord(a.seed, pid, s, d, s_lo[d], s_hi[d]);
       const int m = fa_pa_slot(a, d);
       const int r = rx ? fa_ra_slot(a, d) : -1;
       a.wit_x[(size_t)p * n0 + d] = m >= 0 ? (float)a.values[vi * a.npa + m] : base;
@@ -265,8 +250,8 @@ __global__ void __launch_bounds__(FA_THREADS) fa_falsify_kernel(NetDesc net, Fal
     __syncthreads();
     for (int e = tid; e < kw * n0; e += FA_THREADS) {
       const int j = e / n0, d = e - j * n0;
-      wa[e] = fa_coord(a.seed, pid, widx[j], d, s_lo[d], s_hi[d]);
-      wb[e] = fa_coord(a.seed, pid, widx[kw + j], d, s_lo[d], s_hi[d]);
+      wa[e] = fa_sample_coord(a.seed, pid, widx[j], d, s_lo[d], s_hi[d]);
+      wb[e] = fa_sample_coord(a.seed, pid, widx[kw + j], d, s_lo[d], s_hi[d]);
     }
     for (int j = tid; j < kw; j += FA_THREADS) {
       wok[j] = (z0[widx[j]] > 0.f) && (z0[widx[kw + j]] < 0.f);
@@ -354,7 +339,7 @@ __global__ void __launch_bounds__(FA_THREADS) fa_falsify_kernel(NetDesc net, Fal
     __syncthreads();
     for (int e = tid; e < K * n0; e += FA_THREADS) {
       const int j = e / n0, d = e - j * n0;
-      X[e] = fa_coord(a.seed, pid, sidx[j], d, s_lo[d], s_hi[d]);
+      X[e] = fa_sample_coord(a.seed, pid, sidx[j], d, s_lo[d], s_hi[d]);
     }
     if (rx)
       for (int e = tid; e < K * a.nra; e += FA_THREADS) {

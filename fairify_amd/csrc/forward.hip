@@ -19,9 +19,8 @@
 // accumulator epilogue (counts reduced across the 4 row-groups of a wave with shuffles, one LDS
 // atomic per column per tile).
 #include "args.h"
+#include "launch.h"
 #include "regfwd.h"
-
-#include <stdlib.h>
 
 #define FA_TR 64
 
@@ -597,37 +596,21 @@ SimRegKernel select_sim_reg(int TM) {
 // Compile-time shapes (common.h FaShape): the chains of AC-1 .. AC-12.  Same LDS layout, samples,
 // passes and arithmetic as the run-time-shape kernel of the same tile depth; SimArgs.regcount = 0
 // (FAIRIFY_SIM_REGCOUNT=0, per call) keeps that kernel.
-struct ShapedSim {
-  std::vector<int> dims;
-  SimRegKernel k;
-};
-template <int... D>
-ShapedSim shaped_sim() {
-  using S = FaShape<D...>;
-  return {{D...}, fa_sim_reg_kernel<SimShape<S>::tm(), S>};
-}
 #define FA_SIM_SHAPES(X)                                                                        \
   X(13, 100, 100, 1) X(13, 100, 1) X(13, 64, 32, 16, 8, 4, 1) X(13, 64, 64, 1) X(13, 50, 1)     \
   X(13, 16, 8, 1) X(13, 12, 12, 1) X(13, 10, 10, 10, 10, 1) X(13, 5, 5, 1) X(13, 5, 5, 5, 5, 1)   \
   X(13, 3, 3, 3, 3, 1) X(13, 5, 5, 5, 5, 5, 5, 5, 5, 5, 1)
 SimRegKernel select_sim_shaped(const NetDesc& net) {
-#define FA_SIM_ENTRY(...) shaped_sim<__VA_ARGS__>(),
-  static const std::vector<ShapedSim> v = {FA_SIM_SHAPES(FA_SIM_ENTRY)};
+#define FA_SIM_ENTRY(...) \
+  {0, {__VA_ARGS__}, fa_sim_reg_kernel<SimShape<FaShape<__VA_ARGS__>>::tm(), FaShape<__VA_ARGS__>>},
+  static const std::vector<FaShaped<SimRegKernel>> v = {FA_SIM_SHAPES(FA_SIM_ENTRY)};
 #undef FA_SIM_ENTRY
-  for (const auto& s : v) {
-    if ((int)s.dims.size() != net.n_layers + 1) continue;
-    bool same = true;
-    int noff = 0;
-    for (int l = 0; l <= net.n_layers && same; ++l) {
-      same = s.dims[l] == net.dims[l];
-      if (l < net.n_layers) {
-        same = same && net.neuron_off[l] == noff;   // the constants assume the dense numbering
-        noff += s.dims[l + 1];
-      }
-    }
-    if (same) return s.k;
+  int noff = 0;
+  for (int l = 0; l < net.n_layers; ++l) {
+    if (net.neuron_off[l] != noff) return nullptr;   // the constants assume the dense numbering
+    noff += net.dims[l + 1];
   }
-  return nullptr;
+  return fa_find_shaped(v, net, 0);
 }
 // A/B switch (FAIRIFY_SIM_REG=0: the 64-row LDS tile kernel for every query)
 bool sim_reg_on() {

@@ -19,10 +19,7 @@
 // |W|.(e + g|h|); the epilogue is purely elementwise (no cross-lane traffic).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <map>
-#include <mutex>
-
+#include "launch.h"
 #include "pointfwd.h"
 
 // 7-tile nets: 260 -> 254 VGPRs (spill-free) doubles the waves per SIMD (1 -> 2)
@@ -87,28 +84,20 @@ __global__ void __launch_bounds__(FA_THREADS) __attribute__((amdgpu_waves_per_eu
 namespace {
 typedef void (*PointKernel)(NetDesc, BoundArgs, PointCfg);
 
-PointKernel select_point(int TM) {
-  if (TM <= 1) return fa_point_kernel<1>;
-  if (TM <= 2) return fa_point_kernel<2>;
-  if (TM <= 4) return fa_point_kernel<4>;
-  if (TM <= 7) return fa_point_kernel<7>;
-  // BM-4's 150-wide layer: the unroller gives up on the 10x10-tile body and the operand arrays
-  // live in scratch (656 B/lane), still far cheaper than the IBP fallback, which stages each
-  // layer's W per box row (one 90 KB row per workgroup: G = 1)
-  if (TM <= 10) return fa_point_kernel<10>;
-  return nullptr;   // wider layers: the caller falls back to IBP
-}
+// the run-time-shape instances, one per TM bucket (launch.h fa_tm_bucket).  10 is BM-4's 150-wide
+// layer: the unroller gives up on the 10x10-tile body and the operand arrays live in scratch
+// (656 B/lane), still far cheaper than the IBP fallback, which stages each layer's W per box row
+// (one 90 KB row per workgroup: G = 1)
+#define FA_POINT_TMS(X) X(1) X(2) X(4) X(7) X(10)
 
-int point_cus() {
-  static int cus = 0;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  });
-  return cus;
+PointKernel select_point(int TM) {
+  switch (fa_tm_bucket(TM)) {
+#define FA_POINT_CASE(T) \
+  case T: return fa_point_kernel<T>;
+    FA_POINT_TMS(FA_POINT_CASE)
+#undef FA_POINT_CASE
+    default: return nullptr;   // wider layers: the caller falls back to IBP
+  }
 }
 }  // namespace
 
@@ -117,52 +106,30 @@ int point_cus() {
 // Returns 1 if launched, 0 if the shape is unsupported (caller falls back), <0 on error.
 extern "C" int fa_point_try_launch(const NetDesc& net, BoundArgs a, hipStream_t stream) {
   if (a.R <= 0) return 1;
-  int TM = 1;
-  for (int l = 0; l <= net.n_layers; ++l) TM = std::max(TM, (net.dims[l] + 15) / 16);
-  PointKernel k = select_point(TM);
+  PointKernel k = select_point(fa_widest_tiles(net, 0, net.n_layers));
   if (!k) return 0;
   PointCfg cfg{};
-  int off = 0;
-  for (int l = 0; l < net.n_layers; ++l) {
-    cfg.w_lds[l] = off;
-    off += ((net.dims[l] + 15) / 16) * ((net.dims[l + 1] + 15) / 16) * 256;
-  }
-  for (int l = 0; l < net.n_layers; ++l) {
-    cfg.b_lds[l] = off;
-    off += net.dims[l + 1];
-  }
+  int off = fa_lay_weights(net, net.n_layers, cfg.w_lds, 0);
+  off = fa_lay_biases(net, net.n_layers, cfg.b_lds, off);
   if (((off + 3) & ~3) != net.wperm_floats) return -1;   // layout mismatch with the pre-permuted block
   if ((size_t)net.wperm_floats * sizeof(float) > 150 * 1024) return 0;
   off = net.wperm_floats;
   for (int l = 0; l < net.n_layers; ++l) {
     cfg.bp_lds[l] = off;
-    off += ((net.dims[l + 1] + 15) / 16) * 16;
+    off += fa_tiles(net.dims[l + 1]) * 16;
   }
   const size_t bytes = (size_t)off * sizeof(float);   // <= 150 KB + 16 layers x 10 tiles x 64 B
-  static std::mutex mu;
-  static std::map<std::pair<const void*, size_t>, int> occ;
-  int per_cu = 0;
-  {
-    std::lock_guard<std::mutex> g(mu);
-    const auto key = std::make_pair((const void*)k, bytes);
-    auto it = occ.find(key);
-    if (it == occ.end()) {
-      if (!fa_lds_ok(bytes)) return -4;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, FA_THREADS, bytes) != hipSuccess || per_cu <= 0)
-        per_cu = 1;
-      occ[key] = per_cu;
-    } else {
-      per_cu = it->second;
-    }
-  }
+  const int per_cu = fa_blocks_per_cu((const void*)k, FA_THREADS, bytes);
+  if (!per_cu) return -4;
   const long long tiles = (a.R + 15) / 16;
   long long blocks = (tiles + 3) / 4;
-  const long long cap = (long long)point_cus() * per_cu;
+  const long long cap = (long long)fa_device_cus() * per_cu;
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(FA_THREADS), bytes, stream, net, a, cfg);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 1 : -(int)e;
 }
 
-FA_LDS_REGISTER(FA_LDS_K(fa_point_kernel<1>), FA_LDS_K(fa_point_kernel<2>), FA_LDS_K(fa_point_kernel<4>),
-                FA_LDS_K(fa_point_kernel<7>), FA_LDS_K(fa_point_kernel<10>));
+#define FA_POINT_LDS(T) FA_LDS_K(fa_point_kernel<T>),
+FA_LDS_REGISTER(FA_POINT_TMS(FA_POINT_LDS));
+#undef FA_POINT_LDS

@@ -27,15 +27,8 @@
 // (fa_refine_records), not per column and layer; the rows' boxes are staged in LDS.
 #include <hip/hip_runtime.h>
 
-#include <stdlib.h>
-
-#include <algorithm>
-#include <map>
-#include <mutex>
-#include <utility>
-#include <vector>
-
 #include "args.h"
+#include "launch.h"
 
 // Mode FULL (fa_backward_launch): no forward pass at all -- layer 0 from the box, every hidden layer
 // by back-substitution, then the logit's forms and bounds (the work of crown.hip) in the same
@@ -57,6 +50,9 @@ struct RefineCfg {
                               // kept where tighter than the forward ones (FULL: always)
 };
 
+// wave.h's fa_gam under HIP's default contraction (the same value: see there).  Kept apart because
+// the shared copy, compiled with contraction off, moved the register allocation of two kernels here
+// (fa_refine_kernel<10>: 220 -> 224 VGPRs, fa_refine_kernel<4>: 152 -> 148).
 __device__ __forceinline__ float fa_rgam(int k, float u) {
   const float ku = (float)(k + 2) * u;
   return ku / (1.f - ku) * (1.f + 4.f * u);
@@ -495,49 +491,22 @@ __global__ void __launch_bounds__(256) fa_refine_kernel(NetDesc net, BoundArgs a
 
 namespace {
 typedef void (*RefineKernel)(NetDesc, BoundArgs, RefineCfg);
-RefineKernel select_refine(int TM, bool wg) {
-  if (TM <= 1) return fa_refine_kernel<1>;
-  if (TM <= 2) return fa_refine_kernel<2>;
-  if (TM <= 4) return fa_refine_kernel<4>;
-  if (TM <= 7) return wg ? fa_refine_kernel<7, true> : fa_refine_kernel<7>;
-  if (TM <= 10) return wg ? fa_refine_kernel<10, true> : fa_refine_kernel<10>;
-  return nullptr;
-}
 
-// Compile-time shapes (common.h FaShape): the zoo's deep chains, each instantiated for the TM bucket
-// select_refine picks for it (same LDS layout and arithmetic; the column body is unrolled per layer
-// with constant widths).  FAIRIFY_REFINE_SHAPED=0 (read per launch: the bitwise-equality test toggles
-// it) keeps the run-time-shape kernels.
-struct ShapedRefine {
-  int tm;
-  bool wg;
-  std::vector<int> dims;
-  RefineKernel k;
-};
-template <int TM, int... D>
-ShapedRefine shaped_refine() {
-  return {TM, false, {D...}, fa_refine_kernel<TM, false, FaShape<D...>>};
-}
+// the run-time-shape instances, one per TM bucket (launch.h fa_tm_bucket); the global-weights
+// variant exists for the two wide buckets only
+#define FA_REFINE_TMS(X) X(1) X(2) X(4) X(7) X(10)
+#define FA_REFINE_WG_TMS(X) X(7) X(10)
 
-RefineKernel select_refine_shaped(const NetDesc& net, int TM, bool wg) {
-  const char* e = getenv("FAIRIFY_REFINE_SHAPED");
-  if (e && *e == '0') return nullptr;
-  static const std::vector<ShapedRefine> v = {
-      shaped_refine<4, 13, 64, 32, 16, 8, 4, 1>(),    // AC-7
-      shaped_refine<4, 16, 64, 32, 16, 8, 4, 1>(),    // BM-8
-      shaped_refine<4, 13, 64, 64, 1>(),              // AC-5
-      shaped_refine<7, 13, 100, 100, 1>(),            // AC-4
-      shaped_refine<1, 13, 10, 10, 10, 10, 1>(),      // AC-11
-  };
-  const int tmb = TM <= 1 ? 1 : TM <= 2 ? 2 : TM <= 4 ? 4 : TM <= 7 ? 7 : 10;
-  for (const auto& s : v) {
-    if (s.tm != tmb || s.wg != wg || (int)s.dims.size() != net.n_layers + 1) continue;
-    bool same = true;
-    for (int l = 0; l <= net.n_layers && same; ++l) same = s.dims[l] == net.dims[l];
-    if (same) return s.k;
-  }
-  return nullptr;
-}
+// Compile-time shapes (common.h FaShape) as X(TM bucket, widths...): the zoo's deep chains, each
+// instantiated for the bucket the run-time-shape selection picks for it (same LDS layout and
+// arithmetic; the column body is unrolled per layer with constant widths), staged weights only.
+// A new shape is one line here: the selection table and the LDS registry both come from it.
+#define FA_REFINE_SHAPES(X)                                                                   \
+  X(4, 13, 64, 32, 16, 8, 4, 1) /* AC-7 */                                                    \
+  X(4, 16, 64, 32, 16, 8, 4, 1) /* BM-8 */                                                    \
+  X(4, 13, 64, 64, 1)           /* AC-5 */                                                    \
+  X(7, 13, 100, 100, 1)         /* AC-4 */                                                    \
+  X(1, 13, 10, 10, 10, 10, 1)   /* AC-11 */
 
 // global-weights variant above this many staged bytes (FAIRIFY_REFINE_WG_KB: A/B and the
 // bitwise-equality test; 0 = never; read per launch)
@@ -547,42 +516,58 @@ size_t refine_wg_bytes() {
   return kb > 0 ? (size_t)kb * 1024 : (size_t)-1;
 }
 
-int refine_cus() {
-  static int cus = 0;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  });
-  return cus;
-}
-}  // namespace
+struct RefinePick {
+  RefineKernel k;   // nullptr: a layer too wide for any instance
+  bool wg;          // the global-weights variant
+  bool shaped;
+  int wfloats;      // the LW layers' weights in operand order
+};
 
-namespace {
+// The kernel a launch that needs the first LW layers' weights runs for this network, and those
+// weights' layout (w_lds), for backward_launch and the fa_refine_shaped query alike.
+// FAIRIFY_REFINE_SHAPED=0 (read per launch: the bitwise-equality test toggles it) keeps the
+// run-time-shape kernels.
+RefinePick pick_refine(const NetDesc& net, int LW, int* w_lds) {
+  // the LDS layout, and (WG) the same offsets in the global block
+  const int wfloats = fa_lay_weights(net, LW, w_lds, 0);
+  const int TM = fa_widest_tiles(net, 0, net.n_layers - 1);
+  const int tmb = fa_tm_bucket(TM);
+  const bool wg = (size_t)wfloats * sizeof(float) > refine_wg_bytes() && TM >= 5 && net.wback_floats >= wfloats;
+  if (tmb && !wg && !fa_env_off("FAIRIFY_REFINE_SHAPED")) {
+#define FA_REFINE_ENTRY(TM, ...) {TM, {__VA_ARGS__}, fa_refine_kernel<TM, false, FaShape<__VA_ARGS__>>},
+    static const std::vector<FaShaped<RefineKernel>> v = {FA_REFINE_SHAPES(FA_REFINE_ENTRY)};
+#undef FA_REFINE_ENTRY
+    if (const RefineKernel ks = fa_find_shaped(v, net, tmb)) return {ks, false, true, wfloats};
+  }
+  if (wg) {   // implies TM >= 5: one of the wide buckets, or none
+    switch (tmb) {
+#define FA_REFINE_CASE(T) \
+  case T: return {fa_refine_kernel<T, true>, true, false, wfloats};
+      FA_REFINE_WG_TMS(FA_REFINE_CASE)
+#undef FA_REFINE_CASE
+      default: return {nullptr, true, false, wfloats};
+    }
+  }
+  switch (tmb) {
+#define FA_REFINE_CASE(T) \
+  case T: return {fa_refine_kernel<T>, false, false, wfloats};
+    FA_REFINE_TMS(FA_REFINE_CASE)
+#undef FA_REFINE_CASE
+    default: return {nullptr, false, false, wfloats};
+  }
+}
+
 int backward_launch(const NetDesc& net, const BoundArgs& a, int full, int logit, hipStream_t stream) {
   const int L = net.n_layers;
-  int TM = 1;
-  for (int l = 0; l < L; ++l) TM = std::max(TM, (net.dims[l] + 15) / 16);
   RefineCfg cfg{};
   cfg.full = full;
   cfg.logit = logit;
   const int LW = (full || logit) ? L : L - 1;
-  int offs = 0;
-  for (int l = 0; l < LW; ++l) {
-    cfg.w_lds[l] = offs;   // the LDS layout, and (WG) the same offsets in the global block
-    offs += ((net.dims[l] + 15) / 16) * ((net.dims[l + 1] + 15) / 16) * 256;
-  }
-  const bool wg = (size_t)offs * sizeof(float) > refine_wg_bytes() && TM >= 5 && net.wback_floats >= offs;
-  RefineKernel k = select_refine(TM, wg);
+  const RefinePick pick = pick_refine(net, LW, cfg.w_lds);
+  const RefineKernel k = pick.k;
   if (!k) return -1;
-  if (const RefineKernel ks = select_refine_shaped(net, TM, wg)) k = ks;
-  if (wg) offs = 0;        // nothing staged: the biases start the LDS
-  for (int l = 0; l < LW; ++l) {
-    cfg.b_lds[l] = offs;
-    offs += net.dims[l + 1];
-  }
+  // nothing staged in the global-weights variant: the biases start the LDS
+  const int offs = fa_lay_biases(net, LW, cfg.b_lds, pick.wg ? 0 : pick.wfloats);
   const int base = (offs + 3) & ~3;
   const int N = net.n_neurons, NH = net.n_hidden, n0 = net.dims[0];
   int maxw = 1;
@@ -609,29 +594,23 @@ int backward_launch(const NetDesc& net, const BoundArgs& a, int full, int logit,
   cfg.G = G;
   const size_t bytes = layout(G);
   cfg.floats = (int)(bytes / sizeof(float));
-  if (!fa_lds_ok(bytes)) return -4;
-  static std::mutex mu;
-  static std::map<std::pair<const void*, size_t>, int> occ;
-  int per_cu = 0;
-  {
-    std::lock_guard<std::mutex> g(mu);
-    const auto key = std::make_pair((const void*)k, bytes);
-    auto it = occ.find(key);
-    if (it == occ.end()) {
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, bytes) != hipSuccess || per_cu <= 0) per_cu = 1;
-      occ[key] = per_cu;
-    } else {
-      per_cu = it->second;
-    }
-  }
+  const int per_cu = fa_blocks_per_cu((const void*)k, 256, bytes);
+  if (!per_cu) return -4;
   long long blocks = ((long long)a.R + G - 1) / G;
-  const long long cap = (long long)refine_cus() * per_cu * 4;
+  const long long cap = (long long)fa_device_cus() * per_cu * 4;
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), bytes, stream, net, a, cfg);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : -(int)e - 10;
 }
 }  // namespace
+
+// does a launch for this network run a compile-time-shape instance?  logit: the launches that also
+// do the logit's backward pass (fa_refine_crown_launch, fa_backward_launch) need every layer's weights
+extern "C" int fa_refine_shaped(const NetDesc& net, int logit) {
+  int w_lds[FA_MAX_LAYERS];
+  return pick_refine(net, logit ? net.n_layers : net.n_layers - 1, w_lds).shaped;
+}
 
 // 0 launched (or nothing to refine: fewer than two hidden layers), -1 shape not supported (a layer
 // wider than 160 or the weights beyond the LDS budget: the caller keeps the forward bounds, which
@@ -660,11 +639,11 @@ extern "C" int fa_backward_launch(const NetDesc& net, BoundArgs a, hipStream_t s
   return backward_launch(net, a, 1, 1, stream);
 }
 
-FA_LDS_REGISTER(FA_LDS_K((fa_refine_kernel<7, true>)), FA_LDS_K((fa_refine_kernel<10, true>)));
-FA_LDS_REGISTER(FA_LDS_K(fa_refine_kernel<1>), FA_LDS_K(fa_refine_kernel<2>), FA_LDS_K(fa_refine_kernel<4>),
-                FA_LDS_K(fa_refine_kernel<7>), FA_LDS_K(fa_refine_kernel<10>));
-FA_LDS_REGISTER(FA_LDS_K((fa_refine_kernel<4, false, FaShape<13, 64, 32, 16, 8, 4, 1>>)),
-                FA_LDS_K((fa_refine_kernel<4, false, FaShape<16, 64, 32, 16, 8, 4, 1>>)),
-                FA_LDS_K((fa_refine_kernel<4, false, FaShape<13, 64, 64, 1>>)),
-                FA_LDS_K((fa_refine_kernel<7, false, FaShape<13, 100, 100, 1>>)),
-                FA_LDS_K((fa_refine_kernel<1, false, FaShape<13, 10, 10, 10, 10, 1>>)));
+#define FA_REFINE_LDS(T) FA_LDS_K(fa_refine_kernel<T>),
+#define FA_REFINE_WG_LDS(T) FA_LDS_K((fa_refine_kernel<T, true>)),
+#define FA_REFINE_SHAPE_LDS(TM, ...) FA_LDS_K((fa_refine_kernel<TM, false, FaShape<__VA_ARGS__>>)),
+FA_LDS_REGISTER(FA_REFINE_TMS(FA_REFINE_LDS) FA_REFINE_WG_TMS(FA_REFINE_WG_LDS));
+FA_LDS_REGISTER(FA_REFINE_SHAPES(FA_REFINE_SHAPE_LDS));
+#undef FA_REFINE_LDS
+#undef FA_REFINE_WG_LDS
+#undef FA_REFINE_SHAPE_LDS

@@ -26,33 +26,11 @@
 #include <mutex>
 
 #include "args.h"
+#include "wave.h"
 
 #define ST_UNKNOWN 0
 #define ST_RUNNING 3
 #define ST_STOPPING 4
-
-__device__ __forceinline__ float fa_gamr(int k, float u) {
-  const float ku = (float)(k + 2) * u;
-  return ku / (1.f - ku) * (1.f + 4.f * u);
-}
-
-template <int G>
-__device__ __forceinline__ float fa_gsum(float v) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// (score, index) arg-max within a group; ties -> lower index
-template <int G>
-__device__ __forceinline__ void fa_gargmax(float& s, int& i) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) {
-    const float s2 = __shfl_xor(s, off, 64);
-    const int i2 = __shfl_xor(i, off, 64);
-    if (s2 > s || (s2 == s && i2 < i)) { s = s2; i = i2; }
-  }
-}
 
 #define FA_CP_WAVES 4
 
@@ -90,9 +68,9 @@ __global__ void __launch_bounds__(64 * FA_CP_WAVES) fa_crown_phase_kernel(NetDes
   const float u = net.unit;
   int K = 4 * L + 4;
   for (int l = 0; l < L; ++l) K += 2 * net.dims[l + 1];
-  const float gK = fa_gamr(K, u);
-  const float g0 = fa_gamr(n0 + 1, u);
-  const float g1 = fa_gamr(1, u);
+  const float gK = fa_gam(K, u);
+  const float g0 = fa_gam(n0 + 1, u);
+  const float g1 = fa_gam(1, u);
   const int rows_per_block = FA_CP_WAVES * RPW;
   for (int rb = blockIdx.x * rows_per_block; rb < a.R; rb += gridDim.x * rows_per_block) {
     const int r0 = rb + wave * RPW + grp;
@@ -179,23 +157,23 @@ __global__ void __launch_bounds__(64 * FA_CP_WAVES) fa_crown_phase_kernel(NetDes
               if (sc > lsc || (sc == lsc && off + j < lidx)) { lsc = sc; lidx = off + j; }
             }
           }
-          tsum = fa_gsum<G>(tsum);
-          tmag = fa_gsum<G>(tmag);
-          errc = fa_gsum<G>(errc);
-          erel = fa_gsum<G>(erel);
-          cs = fa_gsum<G>(cs);
-          cm = fa_gsum<G>(cm);
-          eb = fa_gsum<G>(eb);
-          fa_gargmax<G>(lsc, lidx);
-          const float v = (tsum + c) - err * (1.f + 2.f * gK) - fa_gamr(n + 3, u) * (tmag + fabsf(c));
+          tsum = fa_group_sum<G>(tsum);
+          tmag = fa_group_sum<G>(tmag);
+          errc = fa_group_sum<G>(errc);
+          erel = fa_group_sum<G>(erel);
+          cs = fa_group_sum<G>(cs);
+          cm = fa_group_sum<G>(cm);
+          eb = fa_group_sum<G>(eb);
+          fa_group_argmax<G>(lsc, lidx);
+          const float v = (tsum + c) - err * (1.f + 2.f * gK) - fa_gam(n + 3, u) * (tmag + fabsf(c));
           pol_best = fmaxf(pol_best, v);
           err += errc;
           if (lsc > sc_best) { sc_best = lsc; sc_idx = lidx; }
           const float cold = c;
           c = cold + cs;
-          err += erel + fa_gamr(2 * n + 1, u) * (fabsf(cold) + cm) + eb;
+          err += erel + fa_gam(2 * n + 1, u) * (fabsf(cold) + cm) + eb;
           __builtin_amdgcn_wave_barrier();
-          const float gn = fa_gamr(n + 1, u);
+          const float gn = fa_gam(n + 1, u);
           for (int i = gl; i < nin; i += G) {
             float acc = 0.f, q1 = 0.f, q2 = 0.f;
             for (int j = 0; j < n; ++j) {
@@ -220,9 +198,9 @@ __global__ void __launch_bounds__(64 * FA_CP_WAVES) fa_crown_phase_kernel(NetDes
           cp += fminf(lm * xl, lm * xh);
           mp += fabsf(lm) * mx;
         }
-        ein = fa_gsum<G>(ein);
-        cp = fa_gsum<G>(cp);
-        mp = fa_gsum<G>(mp);
+        ein = fa_group_sum<G>(ein);
+        cp = fa_group_sum<G>(cp);
+        mp = fa_group_sum<G>(mp);
         const float err_in = (err + ein) * (1.f + 2.f * gK);
         const float conc = cp + c;
         const float cmg = mp + fabsf(c);

@@ -26,16 +26,10 @@
 // LDS-tiled fa_bounds_kernel; see fa_sym_try_launch.
 #include <hip/hip_runtime.h>
 
-#include <stdlib.h>
-
-#include <algorithm>
-#include <map>
-#include <mutex>
 #include <tuple>
-#include <utility>
-#include <vector>
 
 #include "args.h"
+#include "launch.h"
 
 #define FA_SYM_MAXC 48   // at most 3 column tiles
 
@@ -795,103 +789,110 @@ int max_tm() {
   return v;
 }
 
-SymKernel select_kernel(int NT, int TM) {
-  if (TM > max_tm()) return nullptr;
-  switch (NT) {
-    case 1:
-      if (TM <= 1) return use_pair() ? sym_ptr<1, 1, true>() : sym_ptr<1, 1>();
-      if (TM <= 2) return sym_ptr<1, 2>();
-      if (TM <= 4) return sym_ptr<1, 4>();
-      if (TM <= 7) return sym_ptr<1, 7>();
-      if (TM <= 10) return sym_ptr<1, 10>();   // e.g. BM-4's 150-wide layer (scratch-backed operands)
-      return nullptr;
-    case 2:
-      if (TM <= 1) return sym_ptr<2, 1>();
-      if (TM <= 2) return sym_ptr<2, 2>();
-      if (TM <= 4) return sym_ptr<2, 4>();
-      if (TM <= 10) return sym_ptr<2, 10>();
-      return nullptr;
-    case 3:
-      if (TM <= 1) return sym_ptr<3, 1>();
-      if (TM <= 2) return sym_ptr<3, 2>();
-      return nullptr;
-    default:
-      return nullptr;
-  }
-}
+// the run-time-shape instances as X(NT, TM bucket); besides them the paired kernel sym_ptr<1, 1, true>
+// and the packed ones of select_packed.  10 is e.g. BM-4's 150-wide layer (scratch-backed operands).
+#define FA_SYM_GRID(X) X(1, 1) X(1, 2) X(1, 4) X(1, 7) X(1, 10) X(2, 1) X(2, 2) X(2, 4) X(2, 10) X(3, 1) X(3, 2)
 
-// the TM template bucket select_kernel uses for a layer width of TM tiles (0: none)
+// the TM template bucket of the grid for a layer width of TM tiles (0: none): two column tiles have
+// no 7-tile instance (they take the 10-tile one), three stop at two row tiles
 int tm_bucket(int NT, int TM) {
   if (TM > max_tm()) return 0;
-  const int b = TM <= 1 ? 1 : TM <= 2 ? 2 : TM <= 4 ? 4 : TM <= 7 ? 7 : TM <= 10 ? 10 : 0;
+  const int b = fa_tm_bucket(TM);
   if (NT == 2 && b == 7) return 10;
   if (NT == 3 && b > 2) return 0;
   return NT >= 1 && NT <= 3 ? b : 0;
 }
 
-// Compile-time shapes (SymShape): the zoo's dominant layer chains, each instantiated for the (NT, TM
-// bucket, paired / packed) kernel the run-time selection picks for it, so launch geometry, LDS layout and arithmetic
-// are the generic kernel's.  FAIRIFY_SYM_SHAPED=0 (read per launch: the bitwise-equality test
-// toggles it) keeps the run-time-shape kernels.
-struct ShapedKernel {
-  int nt, tm;
-  bool pair;   // two box rows per wave (single-tile networks)
-  int pg;      // packed: boxes per MFMA tile (1: not packed)
-  std::vector<int> dims;
-  SymKernel k;
-};
-template <int NT, int TM, bool PAIR, int PG, int... D>
-ShapedKernel shaped() {
-  return {NT, TM, PAIR, PG, {D...}, fa_sym_kernel<NT, TM, PAIR, PG, SymShape<D...>>};
-}
-
-const std::vector<ShapedKernel>& shaped_kernels() {
-  static const std::vector<ShapedKernel> v = {
-      shaped<1, 4, false, 1, 13, 64, 32, 16, 8, 4, 1>(),   // AC-7, PA folded (node-row expansion)
-      shaped<2, 4, false, 1, 13, 64, 32, 16, 8, 4, 1>(),   // AC-7, no dim folded (beta tightening rows)
-      shaped<2, 4, false, 1, 16, 64, 32, 16, 8, 4, 1>(),   // BM-8
-      shaped<1, 4, false, 1, 13, 64, 64, 1>(),             // AC-5
-      shaped<1, 4, false, 1, 13, 50, 1>(),                 // AC-3
-      shaped<1, 7, false, 1, 13, 100, 100, 1>(),           // AC-4
-      shaped<1, 7, false, 1, 13, 100, 1>(),                // AC-2
-      // narrow single-tile chains, PA folded (NT = 1): paired (two box rows per wave) ...
-      shaped<1, 1, true, 1, 13, 16, 8, 1>(),               // AC-1
-      shaped<1, 1, true, 1, 13, 12, 12, 1>(),              // AC-6
-      shaped<1, 1, true, 1, 13, 10, 10, 10, 10, 1>(),      // AC-11
-      // ... and packed, two boxes per MFMA tile
-      shaped<1, 1, true, 2, 13, 5, 5, 1>(),                            // AC-8
-      shaped<1, 1, true, 2, 13, 5, 5, 5, 5, 1>(),                      // AC-10
-      // (AC-12's ten unrolled layers spill: 24 VGPRs, 100 B/lane of scratch against 0 for the
-      // run-time-shape kernel -- it keeps the latter)
-  };
-  return v;
-}
-
-SymKernel select_shaped(const NetDesc& net, int NT, int tmb, bool pair, int pg) {
-  const char* e = getenv("FAIRIFY_SYM_SHAPED");
-  if (e && *e == '0') return nullptr;
-  for (const auto& s : shaped_kernels()) {
-    if (s.nt != NT || s.tm != tmb || s.pair != pair || s.pg != pg || (int)s.dims.size() != net.n_layers + 1) continue;
-    bool same = true;
-    for (int l = 0; l <= net.n_layers && same; ++l) same = s.dims[l] == net.dims[l];
-    if (same) return s.k;
+SymKernel select_kernel(int NT, int tmb) {
+  if (NT == 1 && tmb == 1 && use_pair()) return sym_ptr<1, 1, true>();
+  switch (16 * NT + tmb) {
+#define FA_SYM_CASE(NT_, TM_) \
+  case 16 * NT_ + TM_: return sym_ptr<NT_, TM_>();
+    FA_SYM_GRID(FA_SYM_CASE)
+#undef FA_SYM_CASE
+    default: return nullptr;
   }
-  return nullptr;
 }
 
-int device_cus() {
-  static int cus = 0;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  });
-  return cus;
+// Compile-time shapes (SymShape) as X(NT, TM bucket, paired, packed boxes per tile, widths...): the
+// zoo's dominant layer chains, each instantiated for the (NT, TM bucket, paired / packed) kernel the
+// run-time selection picks for it, so launch geometry, LDS layout and arithmetic are the generic
+// kernel's.  A new shape is one line here: the selection table and the LDS registry both come from it.
+#define FA_SYM_SHAPES(X)                                                                              \
+  X(1, 4, false, 1, 13, 64, 32, 16, 8, 4, 1) /* AC-7, PA folded (node-row expansion) */               \
+  X(2, 4, false, 1, 13, 64, 32, 16, 8, 4, 1) /* AC-7, no dim folded (beta tightening rows) */         \
+  X(2, 4, false, 1, 16, 64, 32, 16, 8, 4, 1) /* BM-8 */                                               \
+  X(1, 4, false, 1, 13, 64, 64, 1)           /* AC-5 */                                               \
+  X(1, 4, false, 1, 13, 50, 1)               /* AC-3 */                                               \
+  X(1, 7, false, 1, 13, 100, 100, 1)         /* AC-4 */                                               \
+  X(1, 7, false, 1, 13, 100, 1)              /* AC-2 */                                               \
+  /* narrow single-tile chains, PA folded (NT = 1): paired (two box rows per wave) ... */             \
+  X(1, 1, true, 1, 13, 16, 8, 1)             /* AC-1 */                                               \
+  X(1, 1, true, 1, 13, 12, 12, 1)            /* AC-6 */                                               \
+  X(1, 1, true, 1, 13, 10, 10, 10, 10, 1)    /* AC-11 */                                              \
+  /* ... and packed, two boxes per MFMA tile */                                                       \
+  X(1, 1, true, 2, 13, 5, 5, 1)              /* AC-8 */                                               \
+  X(1, 1, true, 2, 13, 5, 5, 5, 5, 1)        /* AC-10 */
+// (AC-12's ten unrolled layers spill: 24 VGPRs, 100 B/lane of scratch against 0 for the
+// run-time-shape kernel -- it keeps the latter)
+
+constexpr int sym_key(int nt, int tm, bool pair, int pg) { return ((16 * nt + tm) * 2 + (pair ? 1 : 0)) * 8 + pg; }
+
+struct SymPick {
+  SymKernel k;   // nullptr: the caller must use the LDS-tiled kernel
+  int NT, tmb;
+  bool pair;     // two box rows per wave (single-tile networks)
+  int pg;        // packed: boxes per MFMA tile (1: not packed)
+  bool shaped;
+};
+
+// The kernel a launch runs for this network and fold mask, and the column table of cfg, for
+// fa_sym_try_launch and the fa_sym_shaped query alike.  FAIRIFY_SYM_SHAPED=0 (read per launch: the
+// bitwise-equality test toggles it) keeps the run-time-shape kernels.
+SymPick pick_sym(const NetDesc& net, unsigned long long fold_mask, SymCfg& cfg) {
+  SymPick p{};
+  const int n0 = net.dims[0];
+  if (n0 > 64) return p;
+  cfg.fold = fold_mask;
+  int nc = 0;
+  for (int d = 0; d < n0; ++d)
+    if (!((fold_mask >> d) & 1ull)) {
+      if (nc >= FA_SYM_MAXC) return p;
+      cfg.cdim[nc++] = d;
+    }
+  cfg.nc = nc;
+  const int cols = nc + 4;
+  p.NT = (cols + 15) / 16;
+  p.tmb = tm_bucket(p.NT, fa_widest_tiles(net, 0, net.n_layers));
+  SymKernel k = select_kernel(p.NT, p.tmb);
+  if (!k) return p;
+  p.pair = k == sym_ptr<1, 1, true>();
+  // packed narrow networks: pack_g boxes per tile, block-diagonal weights (NetDesc.pack_*)
+  p.pg = (p.pair && net.pack_g > 1 && net.dims[0] <= 16 && use_pack()) ? net.pack_g : 1;
+  if (p.pg > 1) k = select_packed(p.pg);
+  if (!k) return p;
+  // a compile-time-shape instance of the same (NT, TM, paired / packed) kernel, when there is one
+  if (!fa_env_off("FAIRIFY_SYM_SHAPED")) {
+#define FA_SYM_ENTRY(NT, TM, PAIR, PG, ...) \
+  {sym_key(NT, TM, PAIR, PG), {__VA_ARGS__}, fa_sym_kernel<NT, TM, PAIR, PG, SymShape<__VA_ARGS__>>},
+    static const std::vector<FaShaped<SymKernel>> v = {FA_SYM_SHAPES(FA_SYM_ENTRY)};
+#undef FA_SYM_ENTRY
+    if (const SymKernel ks = fa_find_shaped(v, net, sym_key(p.NT, p.tmb, p.pair, p.pg))) {
+      k = ks;
+      p.shaped = true;
+    }
+  }
+  p.k = k;
+  return p;
 }
 
 }  // namespace
+
+// does a launch for this network and fold mask run a compile-time-shape instance?
+extern "C" int fa_sym_shaped(const NetDesc& net, unsigned long long fold_mask) {
+  SymCfg cfg{};
+  return pick_sym(net, fold_mask, cfg).shaped;
+}
 
 // Launch the register-resident kernel if the shape fits; returns 1 if launched, 0 if the caller
 // must use the LDS-tiled kernel, <0 on a launch error.  fold_mask: input dims degenerate in
@@ -899,32 +900,12 @@ int device_cus() {
 extern "C" int fa_sym_try_launch(const NetDesc& net, BoundArgs a, unsigned long long fold_mask,
                                  hipStream_t stream) {
   if (!a.symbolic || a.R <= 0) return 0;
-  const int n0 = net.dims[0];
-  if (n0 > 64) return 0;
   SymCfg cfg{};
-  cfg.fold = fold_mask;
-  int nc = 0;
-  for (int d = 0; d < n0; ++d)
-    if (!((fold_mask >> d) & 1ull)) {
-      if (nc >= FA_SYM_MAXC) return 0;
-      cfg.cdim[nc++] = d;
-    }
-  cfg.nc = nc;
-  const int cols = nc + 4;
-  const int NT = (cols + 15) / 16;
-  int TM = 1;
-  for (int l = 0; l < net.n_layers; ++l) TM = std::max(TM, (net.dims[l] + 15) / 16);
-  TM = std::max(TM, (net.dims[net.n_layers] + 15) / 16);
-  SymKernel k = select_kernel(NT, TM);
+  const SymPick p = pick_sym(net, fold_mask, cfg);
+  const SymKernel k = p.k;
   if (!k) return 0;
-  const bool pair0 = k == sym_ptr<1, 1, true>();
-  const int tmb = tm_bucket(NT, TM);
-  // packed narrow networks: pack_g boxes per tile, block-diagonal weights (NetDesc.pack_*)
-  const int pg = (pair0 && net.pack_g > 1 && net.dims[0] <= 16 && use_pack()) ? net.pack_g : 1;
-  if (pg > 1) k = select_packed(pg);
-  if (!k) return 0;
-  // a compile-time-shape instance of the same (NT, TM, paired / packed) kernel, when there is one
-  if (const SymKernel ks = select_shaped(net, NT, tmb, pair0, pg)) k = ks;
+  const int NT = p.NT, tmb = p.tmb, pg = p.pg;
+  const bool pair0 = p.pair;
   int off = 0;
   if (pg > 1) {
     cfg.w_lds[0] = 0;
@@ -940,14 +921,8 @@ extern "C" int fa_sym_try_launch(const NetDesc& net, BoundArgs a, unsigned long 
     if (off != net.pack_floats) return -1;      // layout mismatch with the packed block
     cfg.stage_off = net.pack_off;
   } else {
-    for (int l = 0; l < net.n_layers; ++l) {
-      cfg.w_lds[l] = off;
-      off += ((net.dims[l] + 15) / 16) * ((net.dims[l + 1] + 15) / 16) * 256;
-    }
-    for (int l = 0; l < net.n_layers; ++l) {
-      cfg.b_lds[l] = off;
-      off += net.dims[l + 1];
-    }
+    off = fa_lay_weights(net, net.n_layers, cfg.w_lds, 0);
+    off = fa_lay_biases(net, net.n_layers, cfg.b_lds, off);
     off = ((off + 3) & ~3);
     if (off != net.wperm_floats) return -1;       // layout mismatch with the pre-permuted block
     cfg.stage_off = net.wperm_off;
@@ -967,45 +942,20 @@ extern "C" int fa_sym_try_launch(const NetDesc& net, BoundArgs a, unsigned long 
   const int rows_per_block = (threads / 64) * (pair0 ? 2 * pg : 1);
   const size_t bytes = (size_t)(off + (threads / 64) * slab) * sizeof(float);
   if (bytes > 160 * 1024) return 0;
-  // per (kernel, LDS bytes): raise the dynamic-LDS limit once and cache the occupancy
-  static std::mutex mu;
-  static std::map<std::pair<const void*, size_t>, int> occ;
-  int per_cu = 0;
-  {
-    std::lock_guard<std::mutex> g(mu);
-    const auto key = std::make_pair((const void*)k, bytes);
-    auto it = occ.find(key);
-    if (it == occ.end()) {
-      if (!fa_lds_ok(bytes)) return -4;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, threads, bytes) != hipSuccess || per_cu <= 0)
-        per_cu = 1;
-      occ[key] = per_cu;
-    } else {
-      per_cu = it->second;
-    }
-  }
+  const int per_cu = fa_blocks_per_cu((const void*)k, threads, bytes);
+  if (!per_cu) return -4;
   long long blocks = (a.R + rows_per_block - 1) / rows_per_block;
-  const long long cap = (long long)device_cus() * per_cu;
+  const long long cap = (long long)fa_device_cus() * per_cu;
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(threads), bytes, stream, net, a, cfg);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 1 : -(int)e;
 }
 
-FA_LDS_REGISTER(FA_LDS_K((sym_ptr<1, 1>())), FA_LDS_K((sym_ptr<1, 1, true>())), FA_LDS_K((sym_ptr<1, 1, true, 2>())),
-                FA_LDS_K((sym_ptr<1, 1, true, 4>())), FA_LDS_K((sym_ptr<1, 2>())), FA_LDS_K((sym_ptr<1, 4>())),
-                FA_LDS_K((sym_ptr<1, 7>())), FA_LDS_K((sym_ptr<1, 10>())), FA_LDS_K((sym_ptr<2, 1>())),
-                FA_LDS_K((sym_ptr<2, 2>())), FA_LDS_K((sym_ptr<2, 4>())), FA_LDS_K((sym_ptr<2, 10>())),
-                FA_LDS_K((sym_ptr<3, 1>())), FA_LDS_K((sym_ptr<3, 2>())));
-FA_LDS_REGISTER(FA_LDS_K((fa_sym_kernel<1, 4, false, 1, SymShape<13, 64, 32, 16, 8, 4, 1>>)),
-                FA_LDS_K((fa_sym_kernel<2, 4, false, 1, SymShape<13, 64, 32, 16, 8, 4, 1>>)),
-                FA_LDS_K((fa_sym_kernel<2, 4, false, 1, SymShape<16, 64, 32, 16, 8, 4, 1>>)),
-                FA_LDS_K((fa_sym_kernel<1, 4, false, 1, SymShape<13, 64, 64, 1>>)),
-                FA_LDS_K((fa_sym_kernel<1, 4, false, 1, SymShape<13, 50, 1>>)),
-                FA_LDS_K((fa_sym_kernel<1, 7, false, 1, SymShape<13, 100, 100, 1>>)),
-                FA_LDS_K((fa_sym_kernel<1, 7, false, 1, SymShape<13, 100, 1>>)));
-FA_LDS_REGISTER(FA_LDS_K((fa_sym_kernel<1, 1, true, 1, SymShape<13, 16, 8, 1>>)),
-                FA_LDS_K((fa_sym_kernel<1, 1, true, 1, SymShape<13, 12, 12, 1>>)),
-                FA_LDS_K((fa_sym_kernel<1, 1, true, 1, SymShape<13, 10, 10, 10, 10, 1>>)),
-                FA_LDS_K((fa_sym_kernel<1, 1, true, 2, SymShape<13, 5, 5, 1>>)),
-                FA_LDS_K((fa_sym_kernel<1, 1, true, 2, SymShape<13, 5, 5, 5, 5, 1>>)));
+#define FA_SYM_LDS(NT, TM) FA_LDS_K((sym_ptr<NT, TM>())),
+#define FA_SYM_SHAPE_LDS(NT, TM, PAIR, PG, ...) FA_LDS_K((fa_sym_kernel<NT, TM, PAIR, PG, SymShape<__VA_ARGS__>>)),
+FA_LDS_REGISTER(FA_SYM_GRID(FA_SYM_LDS) FA_LDS_K((sym_ptr<1, 1, true>())), FA_LDS_K((sym_ptr<1, 1, true, 2>())),
+                FA_LDS_K((sym_ptr<1, 1, true, 4>())));
+FA_LDS_REGISTER(FA_SYM_SHAPES(FA_SYM_SHAPE_LDS));
+#undef FA_SYM_LDS
+#undef FA_SYM_SHAPE_LDS

@@ -20,7 +20,8 @@ def test_no_attribute_calls_on_launch_paths():
 def test_every_checked_launch_file_registers_its_kernels():
     for path in glob.glob(os.path.join(CSRC, "*.hip")):
         src = open(path).read()
-        if "fa_lds_ok(" in src:
+        # fa_blocks_per_cu (csrc/launch.h) asks fa_lds_ok on the caller's behalf
+        if "fa_lds_ok(" in src or "fa_blocks_per_cu(" in src:
             assert "FA_LDS_REGISTER(" in src, os.path.basename(path)
 
 
@@ -31,4 +32,5 @@ def test_registry_populated_at_load():
         import pytest
 
         pytest.skip("extension not built")
-    assert C.lds_registered() >= 40
+    # every instance a launch path can pick: a kernel added to a selection list shows up here
+    assert C.lds_registered() == 127

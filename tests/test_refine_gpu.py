@@ -357,8 +357,14 @@ def test_shaped_refine_kernel_is_bitwise_the_generic_one(cuda, monkeypatch, n0, 
     gpu = Backend(m, cuda)
     L_, H_ = lo.to(cuda), hi.to(cuda)
     outs = []
+    fallback = ext().Net([n0, 17, 3, 5, 3, 1], gpu.unit)      # partial tiles, not instantiated
     for shaped in ("1", "0"):
         monkeypatch.setenv("FAIRIFY_REFINE_SHAPED", shaped)
+        # the launch's own selection, without and with the logit's backward pass: a shaped instance for
+        # every listed shape, none with the switch off, none for a shape the table does not hold
+        for logit in (False, True):
+            assert ext().refine_shaped(H._net(gpu), logit) == (shaped == "1")
+            assert not ext().refine_shaped(fallback, logit)
         a = gpu.bounds(L_, H_, mode="symbolic", crown=True, refine=True)
         f = gpu.bounds(L_, H_, mode="symbolic", keep_layers=True)
         ext().refine_crown(H._net(gpu), **H._bound_kw(gpu, L_, H_, None, f, f.lay_lb_full, f.lay_ub_full)[0])

@@ -36,11 +36,19 @@ def _ident(h):
 @pytest.mark.parametrize("dead", [False, True], ids=["nomask", "mask"])
 @pytest.mark.parametrize("hidden", SHAPED + [FALLBACK], ids=_ident)
 def test_shaped_crown_is_bitwise_the_generic_one(cuda, monkeypatch, hidden, dead):
+    from fairify_amd.ops import ext, hip
+
     # zero biases (the bench's random-init nets: exact zeros decide partitions) and non-zero ones
     for bias in (0.0, 0.3):
         m = random_mlp(13, hidden, seed=53 + len(hidden) + hidden[0], bias_scale=bias)
         be = Backend(m, cuda)
         assert be.hip
+        # the launch's own selection: a shaped instance for every listed shape, none with the switch
+        # off; the fallback shape has none, both runs take the run-time-shape kernel and agree trivially
+        monkeypatch.setenv("FAIRIFY_CROWN_SHAPED", "1")
+        assert ext().crown_shaped(hip._net(be), dead) == (hidden != FALLBACK)
+        monkeypatch.setenv("FAIRIFY_CROWN_SHAPED", "0")
+        assert not ext().crown_shaped(hip._net(be), dead)
         for R in ROWS:
             lo, hi = _boxes(13, R, 23 + R)
             dm = None

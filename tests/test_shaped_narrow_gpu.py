@@ -50,11 +50,21 @@ def _assert_equal(a, b):
 @pytest.mark.parametrize("dead", [False, True])
 @pytest.mark.parametrize("name,hidden", NARROW)
 def test_shaped_narrow_symbolic_is_bitwise_the_generic_one(cuda, monkeypatch, name, hidden, dead):
+    from fairify_amd.ops import ext, hip
+
     # zero biases (the bench's random-init nets: exact zeros decide partitions) and non-zero ones
     for bias in (0.0, 0.3):
         m = random_mlp(13, hidden, seed=31 + len(hidden) + hidden[0], bias_scale=bias)
         be = Backend(m, cuda)
         assert be.hip
+        # the launch's own selection: a shaped instance for every chain but AC-12 (its ten unrolled
+        # layers spill, csrc/symbolic.hip: both runs take the run-time-shape kernel), none with the
+        # switch off
+        fold = hip._fold_mask((PA,), 13)
+        monkeypatch.setenv("FAIRIFY_SYM_SHAPED", "1")
+        assert ext().sym_shaped(hip._net(be), fold) == (name != "AC-12")
+        monkeypatch.setenv("FAIRIFY_SYM_SHAPED", "0")
+        assert not ext().sym_shaped(hip._net(be), fold)
         for R in ROWS:
             lo, hi = _boxes(13, R, 17 + R)
             dm = None
@@ -72,9 +82,17 @@ def test_shaped_narrow_symbolic_is_bitwise_the_generic_one(cuda, monkeypatch, na
 def test_shaped_ac11_refine_is_bitwise_the_generic_one(cuda, monkeypatch, dead):
     """AC-11 (13-10-10-10-10-1), the only narrow model on the refine path: back-substituted hidden
     bounds + backward logit pass with the compile-time-shape refine kernel and with the generic one."""
+    from fairify_amd.ops import ext, hip
+
     for bias in (0.0, 0.3):
         m = random_mlp(13, [10, 10, 10, 10], seed=77, bias_scale=bias)
         be = Backend(m, cuda)
+        # refine=True, crown=True is one launch without and one with the logit's backward pass
+        for logit in (False, True):
+            monkeypatch.setenv("FAIRIFY_REFINE_SHAPED", "1")
+            assert ext().refine_shaped(hip._net(be), logit)
+            monkeypatch.setenv("FAIRIFY_REFINE_SHAPED", "0")
+            assert not ext().refine_shaped(hip._net(be), logit)
         for R in ROWS:
             lo, hi = _boxes(13, R, 5 + R)
             dm = None

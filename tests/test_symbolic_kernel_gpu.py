@@ -77,6 +77,9 @@ def test_symbolic_kernel_matches_reference(cuda, n0, hidden, fold):
     assert rg.dead is not None
 
 
+FALLBACK = [17, 3]          # partial tiles, not instantiated
+
+
 @pytest.mark.parametrize("n0,hidden,fold,dead", [
     (13, [64, 32, 16, 8, 4], (8,), False), (13, [64, 32, 16, 8, 4], (8,), True),    # AC-7
     (13, [64, 32, 16, 8, 4], (), False),                                            # AC-7, NT=2
@@ -86,13 +89,21 @@ def test_symbolic_kernel_matches_reference(cuda, n0, hidden, fold):
 def test_shaped_symbolic_kernel_is_bitwise_the_generic_one(cuda, monkeypatch, n0, hidden, fold, dead):
     """The compile-time-shape instances (csrc/symbolic.hip SymShape: layer loop unrolled, widths
     constant) run the generic kernel's arithmetic: every output is bitwise equal."""
+    from fairify_amd.ops import ext
+    from fairify_amd.ops import hip as H
+
     m = random_mlp(n0, hidden, seed=n0 + len(hidden), bias_scale=0.3)
     lo, hi = _boxes(n0, 700, 9, fold)
     dm = (torch.rand(700, m.n_neurons - 1, generator=torch.Generator().manual_seed(1)) < 0.2).to(cuda) if dead else None
     be = Backend(m, cuda)
     outs = []
+    fallback = ext().Net([n0] + FALLBACK + [1], be.unit)
     for shaped in ("1", "0"):
         monkeypatch.setenv("FAIRIFY_SYM_SHAPED", shaped)
+        # the launch's own selection: a shaped instance for every listed shape, none with the switch
+        # off, none for a shape the table does not hold
+        assert ext().sym_shaped(H._net(be), H._fold_mask(fold, n0)) == (shaped == "1")
+        assert not ext().sym_shaped(fallback, H._fold_mask(fold, n0))
         outs.append(be.bounds(lo.to(cuda), hi.to(cuda), mode="symbolic", keep_layers=True, fold=fold, dead=dm))
     a, b = outs
     for x, y in [(a.out_lb, b.out_lb), (a.out_ub, b.out_ub), (a.Lc, b.Lc), (a.Uc, b.Uc), (a.L0, b.L0), (a.U0, b.U0),
