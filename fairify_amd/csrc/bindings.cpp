@@ -32,6 +32,7 @@ extern "C" int fa_forward_launch(const NetDesc& net, FwdArgs a, hipStream_t stre
 extern "C" int fa_sim_launch(const NetDesc& net, SimArgs a, hipStream_t stream);
 extern "C" int fa_sim_shaped(const NetDesc& net);
 extern "C" int fa_sym_shaped(const NetDesc& net, unsigned long long fold_mask);
+extern "C" int fa_sym_geometry(const NetDesc& net, unsigned long long fold_mask, int* out);
 extern "C" int fa_crown_shaped(const NetDesc& net, int mask);
 extern "C" int fa_refine_shaped(const NetDesc& net, int logit);
 extern "C" int fa_rate_launch(const NetDesc& net, RateArgs a, hipStream_t stream);
@@ -297,6 +298,16 @@ PYBIND11_MODULE(_C, m) {
     a.fold = k.u64("fold", 0);
     a.phase_in = k.ptr<const int8_t>("phase_in");
     a.infeas = k.ptr<uint8_t>("infeas");
+    // the BaB runtimes' launch form, for tests: node-row expansion (row r = node r / V with its PA
+    // dims set to values[r % V]) and the status filter
+    a.V = k.i("V", 0);
+    if (a.V > 0) {
+      a.npa = dims(k, "pa", a.pa_idx, FA_MAX_PA, "bounds: too many protected attributes");
+      a.values = k.need<const float>("values");
+    }
+    a.skip_status = k.ptr<const int8_t>("skip_status");
+    a.skip_part = k.ptr<const int>("skip_part");
+    if (a.skip_status && !a.skip_part) throw std::invalid_argument("bounds: skip_status without skip_part");
     ckl(fa_bounds_launch(net.d, a, finish(k)), "bounds");
   });
 
@@ -400,6 +411,22 @@ PYBIND11_MODULE(_C, m) {
   // switches included): symbolic by fold mask, crown with / without a forced-dead mask, refine
   // without / with the logit's backward pass (refine / refine_crown and backward_bounds)
   m.def("sym_shaped", [](const Net& net, unsigned long long fold) { return fa_sym_shaped(net.d, fold) != 0; });
+  // launch geometry of the register-resident symbolic kernel for this network and fold mask (needs a
+  // device: the occupancy query); None when the launch would take the LDS-tiled kernel
+  m.def("sym_geometry", [](const Net& net, unsigned long long fold) -> py::object {
+    int g[8] = {0};
+    if (fa_sym_geometry(net.d, fold, g) != 1) return py::none();
+    py::dict d;
+    d["threads"] = g[0];
+    d["lds_bytes"] = g[1];
+    d["blocks_per_cu"] = g[2];
+    d["cus"] = g[3];
+    d["rows_per_block"] = g[4];
+    d["waves_per_simd"] = g[5];
+    d["shaped"] = g[6] != 0;
+    d["regs"] = g[7];
+    return d;
+  });
   m.def("crown_shaped", [](const Net& net, bool mask) { return fa_crown_shaped(net.d, mask) != 0; });
   m.def("refine_shaped", [](const Net& net, bool logit) { return fa_refine_shaped(net.d, logit) != 0; });
 

@@ -55,6 +55,33 @@ using SymShapeAny = FaShapeAny;
 template <int... D>
 using SymShape = FaShape<D...>;
 
+// The staged block's LDS layout as a function of the widths alone: what fa_lay_weights /
+// fa_lay_biases (launch.h) and the host's SymCfg set-up compute at run time, and NetDesc::neuron_off.
+// The unpacked (PG == 1) shaped instances take these as constants instead of reading the SymCfg /
+// NetDesc tables (their kernel arguments stayed live in SGPRs across the whole unrolled row);
+// pick_sym checks the run-time values against them before it picks a shaped instance.
+template <class S>
+struct SymLay {
+  __host__ __device__ static constexpr int tiles(int n) { return (n + 15) >> 4; }
+  __host__ __device__ static constexpr int w(int l) {
+    int off = 0;
+    for (int i = 0; i < l; ++i) off += tiles(S::dim(i)) * tiles(S::dim(i + 1)) * 256;
+    return off;
+  }
+  __host__ __device__ static constexpr int b(int l) {
+    int off = w(S::L);
+    for (int i = 0; i < l; ++i) off += S::dim(i + 1);
+    return off;
+  }
+  __host__ __device__ static constexpr int noff(int l) {
+    int off = 0;
+    for (int i = 0; i < l; ++i) off += S::dim(i + 1);
+    return off;
+  }
+  static constexpr int STAGE = (b(S::L) + 3) & ~3;       // staged floats (multiple of 4)
+  static constexpr int LDS = STAGE + FA_SYM_MAXC;         // + column -> input-dim table
+};
+
 struct SymBox {
   const BoundArgs* a;
   int node, v, n0;
@@ -141,7 +168,10 @@ __device__ __forceinline__ void fa_pq_to_ul(const f32x4& P, const f32x4& Q, int 
   }
 }
 
-template <int NT, bool PAIR, int PG = 1, bool CR = false, class S = SymShapeAny>
+//
+// MASK = false (launches without dead_in / dead_part / phase_in / dead_out, e.g. every BaB bounding
+// launch without heuristic masks): no pointer tests, no mask loads, no infeas / dead_out stores.
+template <int NT, bool PAIR, int PG = 1, bool CR = false, class S = SymShapeAny, bool MASK = true>
 __device__ __forceinline__ bool fa_sym_epilogue(const NetDesc& net, const BoundArgs& a, const SymCfg& cfg,
                                                 const float* smem, float* T, const float* bxv_in, const int* cdim_s,
                                                 int l, int r_in, int node_in, int r2, int node2, bool v2, int lane,
@@ -150,9 +180,10 @@ __device__ __forceinline__ bool fa_sym_epilogue(const NetDesc& net, const BoundA
                                                 float (&nlo)[2][NT][4]) {
   constexpr int TS = SymSlab<NT>::TS;
   constexpr bool CS = S::L > 0;        // compile-time shape: l is a constant here (fa_sym_layers_c)
+  constexpr bool CL = CS && PG == 1;   // ... and so is the staged block's layout (SymLay)
   const int col = lane & 15, grp = lane >> 4;
   const int n_out = CS ? S::dim(l + 1) : net.dims[l + 1];
-  const float* sb = smem + cfg.b_lds[l];
+  const float* sb = smem + (CL ? SymLay<S>::b(l) : cfg.b_lds[l]);
   const bool last = CS ? l == S::L - 1 : l == net.n_layers - 1;
   const float gg = net.g_gemm[l];
   const float gc = net.g_conc;
@@ -160,7 +191,7 @@ __device__ __forceinline__ bool fa_sym_epilogue(const NetDesc& net, const BoundA
   const float unit = net.unit;
   // next layer's rounding budget; C/R: gamma_{n_in + 3} (n_in + 2 roundings), charged on both blocks
   const float gnext = last ? 0.f : (CR ? net.g_fwd[l + 1] : net.g_gemm[l + 1]);
-  const int noff = net.neuron_off[l];
+  const int noff = CL ? SymLay<S>::noff(l) : net.neuron_off[l];
   const int nc = cfg.nc;
   const int n0 = CS ? S::dim(0) : net.dims[0];
   // neuron lane role in the epilogue: tile jt0 + (lane >> 5); within it lanes 0-15 = U block,
@@ -239,21 +270,45 @@ __device__ __forceinline__ bool fa_sym_epilogue(const NetDesc& net, const BoundA
       else a.layer_lb[(size_t)r * net.n_neurons + noff + j] = lb;
     }
     if (last) {
-      if (nl_act && j == 0) {   // logit: rigorous bounds + output forms (folded dims -> 0)
-        float* Cf = ob == 0 ? a.Uc : a.Lc;
-        if (ob == 0) {
-          a.out_ub[r] = ub; a.U0[r] = c0; a.Ue[r] = e;
-        } else {
-          a.out_lb[r] = lb; a.L0[r] = c0; a.Le[r] = e;
+      if (PG > 1) {
+        if (nl_act && j == 0) {   // logit: rigorous bounds + output forms (folded dims -> 0)
+          float* Cf = ob == 0 ? a.Uc : a.Lc;
+          if (ob == 0) {
+            a.out_ub[r] = ub; a.U0[r] = c0; a.Ue[r] = e;
+          } else {
+            a.out_lb[r] = lb; a.L0[r] = c0; a.Le[r] = e;
+          }
+          for (int d = 0; d < n0; ++d)
+            if ((cfg.fold >> d) & 1ull) Cf[(size_t)r * n0 + d] = 0.f;
+          for (int c = 0; c < nc; ++c) Cf[(size_t)r * n0 + cdim_s[c]] = Trow[4 + c];
         }
-        for (int d = 0; d < n0; ++d)
-          if ((cfg.fold >> d) & 1ull) Cf[(size_t)r * n0 + d] = 0.f;
-        for (int c = 0; c < nc; ++c) Cf[(size_t)r * n0 + cdim_s[c]] = Trow[4 + c];
+      } else if (nl_act && jt == 0) {
+        // logit (neuron 0 of tile 0; r is uniform over its 16-lane group): lane col == 0 writes the
+        // rigorous bounds and the constants, lane col the coefficient of input dim col (+ 16, ...)
+        // of the block's form -- one coalesced store per 16 dims instead of a serial loop of one
+        // lane.  A dim is folded (0) or has coefficient column d - #folded dims below d (pick_sym
+        // lists the non-folded dims in increasing order).
+        if (col == 0) {
+          if (ob == 0) {
+            a.out_ub[r] = ub; a.U0[r] = c0; a.Ue[r] = e;
+          } else {
+            a.out_lb[r] = lb; a.L0[r] = c0; a.Le[r] = e;
+          }
+        }
+        float* Cf = (ob == 0 ? a.Uc : a.Lc) + (size_t)r * n0;
+        const float* row0 = T + tsub * SymSlab<NT>::TILE1 + (ob * 16) * TS + fa_trot(ob * 16) + 4;
+        const unsigned long long fold = cfg.fold;
+        for (int d = col; d < n0; d += 16) {
+          const bool folded = (fold >> d) & 1ull;
+          const int c = d - __popcll(fold & ((1ull << d) - 1ull));
+          const float x = row0[folded ? 0 : c];
+          Cf[d] = folded ? 0.f : x;
+        }
       }
       return false;
     }
     bool forced = false, fact = false;
-    if (nl_act && jv) {
+    if (MASK && nl_act && jv) {
       if (a.dead_in) forced = a.dead_in[(size_t)r * net.n_hidden + noff + j] != 0;
       else if (a.dead_part) forced = a.dead_part[(size_t)a.node_part[node] * net.n_hidden + noff + j] != 0;
       if (a.phase_in) {   // ReLU-phase rows: fixed inactive = forced dead, fixed active = no chord
@@ -265,7 +320,7 @@ __device__ __forceinline__ bool fa_sym_epilogue(const NetDesc& net, const BoundA
     }
     const bool isdead = ub <= 0.f;
     const bool isact = lb >= 0.f;
-    if (nl_act && ob == 0 && jv && a.dead_out) a.dead_out[(size_t)r * net.n_hidden + noff + j] = isdead ? 1 : 0;
+    if (MASK && nl_act && ob == 0 && jv && a.dead_out) a.dead_out[(size_t)r * net.n_hidden + noff + j] = isdead ? 1 : 0;
     const bool zero = isdead || forced || !jv;
     // both blocks' relaxations, then a per-lane select: the U and L lanes share every wave, so
     // a branch on ob runs both sides anyway, plus the exec-mask juggling (SALU)
@@ -326,7 +381,7 @@ __device__ __forceinline__ bool fa_sym_epilogue(const NetDesc& net, const BoundA
 // index) is the box, both use output tile 0 of W.  PG > 1 (packed, PAIR only): slot u is a group
 // of PG boxes sharing the tile (block-diagonal weights); layer 0 builds its identity-form
 // operands on the fly from the boxes' input ranges in the wave's LDS box table.
-template <int NT, int TM, bool PAIR, int PG = 1, class S = SymShapeAny>
+template <int NT, int TM, bool PAIR, int PG = 1, class S = SymShapeAny, bool MASK = true>
 __device__ __forceinline__ void fa_sym_layer(const NetDesc& net, const BoundArgs& a, const SymCfg& cfg,
                                              const float* smem, float* T, const float* bxv, const int* cdim_s,
                                              int l, int r, int node, int r2, int node2, bool v2, int lane,
@@ -336,23 +391,15 @@ __device__ __forceinline__ void fa_sym_layer(const NetDesc& net, const BoundArgs
   constexpr bool CR = SymForm<PAIR, TM>::CR;
   constexpr int TS = SymSlab<NT>::TS;
   constexpr bool CS = S::L > 0;        // compile-time shape: l is a constant here (fa_sym_layers_c)
+  constexpr bool CL = CS && PG == 1;   // ... and so is the staged block's layout (SymLay)
   const int col = lane & 15, grp = lane >> 4;
   const int n_in = CS ? S::dim(l) : net.dims[l], n_out = CS ? S::dim(l + 1) : net.dims[l + 1];
   const int tin = (n_in + 15) >> 4, tout = (n_out + 15) >> 4;
-  const float* sw = smem + cfg.w_lds[l];
-  const float* sb = smem + cfg.b_lds[l];
+  const float* sw = smem + (CL ? SymLay<S>::w(l) : cfg.w_lds[l]);
   const bool last = CS ? l == S::L - 1 : l == net.n_layers - 1;
   const float gg = net.g_gemm[l];
-  const float gc = net.g_conc;
-  const float gi = net.g_one;
-  const float unit = net.unit;
-  const float gnext = last ? 0.f : net.g_gemm[l + 1];
-  const int noff = net.neuron_off[l];
   const int nc = cfg.nc;
   const int n0 = CS ? S::dim(0) : net.dims[0];
-  // neuron lane role in the epilogue: lanes 0-15 = U block, 16-31 = L block of neuron (lane & 15)
-  const bool nl_act = lane < 32;
-  const int ob = (lane >> 4) & 1;
 #ifndef FA_SYM_TIMING_NO_EPILOGUE
   if (PG > 1 && l == 0) {
     // packed layer 0: group u accumulates its PG boxes, box g through tile g of the packed W_0
@@ -404,7 +451,7 @@ __device__ __forceinline__ void fa_sym_layer(const NetDesc& net, const BoundArgs
       }
     }
     float nu[2][NT][4], nlo[2][NT][4];
-    if (!fa_sym_epilogue<NT, PAIR, PG, CR, S>(net, a, cfg, smem, T, bxv, cdim_s, l, r, node, r2, node2, v2, lane, 0, U, Lq,
+    if (!fa_sym_epilogue<NT, PAIR, PG, CR, S, MASK>(net, a, cfg, smem, T, bxv, cdim_s, l, r, node, r2, node2, v2, lane, 0, U, Lq,
                                        nu, nlo))
       return;
 #pragma unroll
@@ -469,7 +516,7 @@ __device__ __forceinline__ void fa_sym_layer(const NetDesc& net, const BoundArgs
         if (CR) fa_pq_to_ul(f32x4(U[bi][ct]), f32x4(Lq[bi][ct]), ct * 16 + col, gg, U[bi][ct], Lq[bi][ct]);
       }
     float nu[2][NT][4], nlo[2][NT][4];
-    fa_sym_epilogue<NT, PAIR, PG, CR, S>(net, a, cfg, smem, T, bxv, cdim_s, l, r, node, r2, node2, v2, lane, 0, U, Lq,
+    fa_sym_epilogue<NT, PAIR, PG, CR, S, MASK>(net, a, cfg, smem, T, bxv, cdim_s, l, r, node, r2, node2, v2, lane, 0, U, Lq,
                                   nu, nlo);
     return;
   }
@@ -535,7 +582,7 @@ __device__ __forceinline__ void fa_sym_layer(const NetDesc& net, const BoundArgs
       continue;
     }
 #else
-    if (!fa_sym_epilogue<NT, PAIR, PG, CR, S>(net, a, cfg, smem, T, bxv, cdim_s, l, r, node, r2, node2, v2, lane, jt0, U,
+    if (!fa_sym_epilogue<NT, PAIR, PG, CR, S, MASK>(net, a, cfg, smem, T, bxv, cdim_s, l, r, node, r2, node2, v2, lane, jt0, U,
                                        Lq, nu, nlo))
       continue;
 #endif
@@ -561,6 +608,10 @@ __device__ __forceinline__ void fa_sym_layer(const NetDesc& net, const BoundArgs
 // at one block per CU, so its workgroups carry 8 waves (FA_SYM_BIG_THREADS): 3.98 -> 2.89 ms.  The
 // 4-tile kernel at 3 waves (244 B/lane scratch): AC-5 1.297 -> 1.237, AC-7 1.363 -> 1.292 ms
 // (tools/ab_micro.sh, profiles/r2/s3/).
+// These are the TM buckets' settings: the run-time-shape kernels use them as they are, a shaped
+// instance may carry its own (SymTune below).  With their layout constant the shaped 4-tile
+// instances (AC-7, AC-5, AC-3) need 145-167 VGPRs, so three workgroups of theirs fit a CU under
+// the limit of 2; an explicit 3 measured 1-3 % slower (profiles/r16/sym_wide/).
 #ifndef FA_SYM_WPE7
 #define FA_SYM_WPE7 2
 #endif
@@ -573,16 +624,16 @@ __device__ __forceinline__ void fa_sym_layer(const NetDesc& net, const BoundArgs
 
 // The layer chain of a compile-time shape: one inlined fa_sym_layer per layer, l a constant in each,
 // operands ping-ponging between XA (even layers' input) and XB.
-template <int NT, int TM, bool PAIR, int PG, class S, int... LS>
+template <int NT, int TM, bool PAIR, int PG, class S, bool MASK, int... LS>
 __device__ __forceinline__ void fa_sym_layers_c(std::integer_sequence<int, LS...>, const NetDesc& net,
                                                 const BoundArgs& a, const SymCfg& cfg, const float* smem, float* T,
                                                 const float* bxv, const int* cdim_s, int r, int node, int r2,
                                                 int node2, bool v2, int lane, float (&XA)[NT][PAIR ? 2 : TM][2][4],
                                                 float (&XB)[NT][PAIR ? 2 : TM][2][4]) {
-  ((LS & 1 ? fa_sym_layer<NT, TM, PAIR, PG, S>(net, a, cfg, smem, T, bxv, cdim_s, LS, r, node, r2, node2, v2, lane,
-                                               XB, XA)
-           : fa_sym_layer<NT, TM, PAIR, PG, S>(net, a, cfg, smem, T, bxv, cdim_s, LS, r, node, r2, node2, v2, lane,
-                                               XA, XB)),
+  ((LS & 1 ? fa_sym_layer<NT, TM, PAIR, PG, S, MASK>(net, a, cfg, smem, T, bxv, cdim_s, LS, r, node, r2, node2, v2,
+                                                     lane, XB, XA)
+           : fa_sym_layer<NT, TM, PAIR, PG, S, MASK>(net, a, cfg, smem, T, bxv, cdim_s, LS, r, node, r2, node2, v2,
+                                                     lane, XA, XB)),
    ...);
 }
 
@@ -593,32 +644,98 @@ __device__ __forceinline__ void fa_sym_layers_c(std::integer_sequence<int, LS...
 #endif
 #define FA_SYM_THREADS(TM) ((TM) == 7 ? FA_SYM_BIG_THREADS : FA_THREADS)
 
-template <int NT, int TM, bool PAIR, int PG = 1, class S = SymShapeAny>
-__global__ void __launch_bounds__(FA_SYM_THREADS(TM)) __attribute__((amdgpu_waves_per_eu(FA_SYM_WAVES_PER_EU(NT, TM, PAIR))))
-fa_sym_kernel(NetDesc net, BoundArgs a, SymCfg cfg) {
+// the unpaired shaped instances' row loop with the next row's box and status fetched ahead (0: the plain loop)
+#ifndef FA_SYM_PREFETCH
+#define FA_SYM_PREFETCH 1
+#endif
+
+// Workgroup size and register limit (waves per SIMD) of an instance: the TM bucket's for the
+// run-time-shape kernels, chosen per shape for the shaped instances (specialisations below the
+// shape list's measurements, docs/DESIGN.md section 5).
+template <int NT, int TM, bool PAIR, class S>
+struct SymTune {
+  static constexpr int THREADS = FA_SYM_THREADS(TM);
+  static constexpr int WPE = FA_SYM_WAVES_PER_EU(NT, TM, PAIR);
+};
+#define FA_SYM_TUNE(NT, TM, THREADS_, WPE_, ...)            \
+  template <>                                                \
+  struct SymTune<NT, TM, false, FaShape<__VA_ARGS__>> {      \
+    static constexpr int THREADS = THREADS_;                 \
+    static constexpr int WPE = WPE_;                         \
+  };
+// AC-2 (14 KB of staged W): three 4-wave workgroups per CU instead of one 8-wave one, 28 B/lane of
+// scratch: 0.526 -> 0.449 ms per 131 072 rows.  Tried and not kept (profiles/r16/sym_wide/): AC-4 at
+// 768 threads / 3 waves (184 B/lane of scratch: mask-free launch 1.53 -> 1.50 ms, masked 1.59 -> 1.63);
+// an explicit limit of 3 for AC-7 / AC-5 / AC-3, whose instances already fit 168 VGPRs under the
+// 4-tile bucket's limit of 2 and so run three workgroups per CU (0.65 -> 0.66, 0.62 -> 0.63, 0.27 -> 0.28).
+FA_SYM_TUNE(1, 7, 256, 3, 13, 100, 1)
+
+// Box values of a coefficient column's range [l0, h0], written to bv[lane] (mid), bv[MAXC + lane]
+// (rad), bv[2 MAXC + lane] (m).  Centre / radius / magnitude are exact for lattice boxes (integers
+// below 2^22); any other range is enclosed outward ([mid - rad, mid + rad] contains it and
+// m >= |mid| + rad), which keeps every bound sound.
+__device__ __forceinline__ void fa_sym_box_values(float l0, float h0, float* bv, int lane) {
+  float mid = 0.5f * (l0 + h0), rad = 0.5f * (h0 - l0), mm = fmaxf(fabsf(l0), fabsf(h0));
+  const bool lattice = l0 == rintf(l0) && h0 == rintf(h0) && fabsf(l0) < 4194304.f && fabsf(h0) < 4194304.f;
+  if (!lattice) {
+    rad = nextafterf(fmaxf(h0 - mid, mid - l0), INFINITY);
+    mm = nextafterf(fabsf(mid) + rad, INFINITY);
+  }
+  bv[lane] = mid;
+  bv[FA_SYM_MAXC + lane] = rad;
+  bv[2 * FA_SYM_MAXC + lane] = mm;
+}
+
+// Layer-0 operands XA[.][t][.][i] of input dim k with range [xl, xh] (kv: k < n0): identity forms
+// (folded dims -> constant) + [hi | lo] interval rows; L-block error columns negated.  One
+// definition for both row loops: they differ only in where xl / xh come from.
+template <int NT, bool CR, int TMS>
+__device__ __forceinline__ void fa_sym_operand0(float xl, float xh, bool kv, bool folded, int k, float g0,
+                                                const int (&role)[NT], const int (&cdm)[NT],
+                                                float (&XA)[NT][TMS][2][4], int t, int i) {
+  const float m = fmaxf(fabsf(xl), fabsf(xh));
+#pragma unroll
+  for (int ct = 0; ct < NT; ++ct) {
+    float vu = 0.f, vl = 0.f;
+    if (kv) {
+      switch (role[ct]) {
+        // C/R kernels: (vu, vl) hold the centre / radius of the [upper | lower] operand pair
+        case 0: vu = (!folded && cdm[ct] == k) ? 1.f : 0.f; vl = CR ? 0.f : vu; break;
+        case 1: vu = folded ? xl : 0.f; vl = CR ? 0.f : vu; break;
+        case 2: vu = CR ? 0.f : g0 * m; vl = CR ? g0 * m : -vu; break;
+        case 3:
+          vu = CR ? 0.5f * (xh + xl) : xh;
+          vl = CR ? 0.5f * (xh - xl) : xl;
+          break;
+        case 4:
+          vu = CR ? 0.5f * g0 * (fabsf(xh) - fabsf(xl)) : g0 * fabsf(xh);
+          vl = CR ? 0.5f * g0 * (fabsf(xh) + fabsf(xl)) : -(g0 * fabsf(xl));
+          break;
+        default: break;
+      }
+    }
+    XA[ct][t][0][i] = vu;
+    XA[ct][t][1][i] = vl;
+  }
+}
+
+// The persistent row loop of one wave (the whole kernel behind the one-time staging).
+template <int NT, int TM, bool PAIR, int PG, class S, bool MASK>
+__device__ __forceinline__ void fa_sym_rows(const NetDesc& net, const BoundArgs& a, const SymCfg& cfg, float* smem,
+                                            const int* cdim_s, int lds_floats) {
+  constexpr int THREADS = SymTune<NT, TM, PAIR, S>::THREADS;
   constexpr bool CR = SymForm<PAIR, TM>::CR;   // centre / radius operands (multi-tile kernels)
   constexpr int TMS = PAIR ? 2 : TM;   // operand slots: K tiles, or (PAIR) the wave's two boxes /
                                        // (packed) two groups of PG boxes
-  extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x;
-  // ---- stage the MFMA-operand-order weights + biases (pre-permuted in `flat`; the block-diagonal
-  //      packed copy when PG > 1) into LDS
-  {
-    const float4* src = reinterpret_cast<const float4*>(a.flat + cfg.stage_off);
-    float4* dst = reinterpret_cast<float4*>(smem);
-    for (int e = tid; e < (cfg.stage_floats >> 2); e += FA_SYM_THREADS(TM)) dst[e] = src[e];
-  }
-  int* cdim_s = reinterpret_cast<int*>(smem + cfg.lds_floats - FA_SYM_MAXC);
-  for (int c = tid; c < FA_SYM_MAXC; c += FA_SYM_THREADS(TM)) cdim_s[c] = c < cfg.nc ? cfg.cdim[c] : -1;
-  __syncthreads();
   const int lane = tid & 63;
   const int grp = lane >> 4;
   const int wave = tid >> 6;
-  const int nw = FA_SYM_THREADS(TM) / 64;
+  const int nw = THREADS / 64;
   const int n0 = S::L > 0 ? S::dim(0) : net.dims[0];
   const int nc = cfg.nc;
   const float g0 = net.g_gemm[0];
-  float* T = smem + cfg.lds_floats + wave * SymSlab<NT, PG>::FLOATS;
+  float* T = smem + lds_floats + wave * SymSlab<NT, PG>::FLOATS;
   float* bxv = T + SymSlab<NT>::TILE;             // [lo | hi | max(|lo|,|hi|)] per coefficient column
   const int tin0 = (n0 + 15) >> 4;
   // column layout: 0 constant, 1 error, 2 interval, 3 interval error, 4.. coefficients
@@ -630,6 +747,89 @@ fa_sym_kernel(NetDesc net, BoundArgs a, SymCfg cfg) {
     cdm[ct] = (role[ct] == 0) ? cdim_s[c - 4] : -1;
   }
   constexpr int RPW = PAIR ? 2 * PG : 1;   // box rows per wave and pass
+  if constexpr (!PAIR && S::L > 0 && FA_SYM_PREFETCH) {
+    // One row per pass, its prologue off the critical path.  Lane d carries input dim d of the row's
+    // box (n0 <= 64) with the PA value substituted, the PA slot resolved once; the NEXT row's box
+    // (two VGPRs) and status are loaded before the current row's layer chain and committed to the
+    // wave's LDS box table [lo 64 | hi 64] (the unused second box of bxv) when their row starts, so a
+    // row waits for no global load of its own.  The status lookup skip_part -> skip_status is two
+    // dependent loads: the partition index is fetched two rows ahead, the status one row ahead.
+    float* btab = bxv + SymSlab<NT>::BOX;
+    static_assert(SymSlab<NT>::BOX >= 128, "box table in the second box's slot");
+    static_assert(S::dim(0) <= 64, "lane d carries input dim d");
+    const int V = a.V, R = a.R;
+    int pslot = -1;
+    if (V > 0)
+      for (int k = 0; k < a.npa; ++k)
+        if (a.pa_idx[k] == lane) pslot = k;
+    const int dl = min(lane, n0 - 1);
+    const int stride = gridDim.x * nw;
+    const bool filt = a.skip_status != nullptr;
+    auto node_of = [&](int rr) { return V > 0 ? rr / V : rr; };
+    auto fetch = [&](int rr, int node, float& blo, float& bhi) {
+      blo = a.lo[(size_t)node * n0 + dl];
+      bhi = a.hi[(size_t)node * n0 + dl];
+      if (pslot >= 0) blo = bhi = a.values[(rr - node * V) * a.npa + pslot];
+    };
+    int r = __builtin_amdgcn_readfirstlane(blockIdx.x * nw + wave);
+    float blo = 0.f, bhi = 0.f;
+    int st = 3, part1 = 0;   // status of row r; partition of row r + stride
+    int node = 0;
+    if (r < R) {
+      node = node_of(r);
+      fetch(r, node, blo, bhi);
+      if (filt) st = a.skip_status[a.skip_part[node]];
+      if (filt && r + stride < R) part1 = a.skip_part[node_of(r + stride)];
+    }
+    for (; r < R; r += stride) {
+      const int rn = r + stride;
+      float nlo = 0.f, nhi = 0.f;
+      int nst = 3, part2 = 0, nnode = 0;
+      if (rn < R) {
+        nnode = node_of(rn);
+        fetch(rn, nnode, nlo, nhi);
+        if (filt) nst = a.skip_status[part1];
+        if (filt && rn + stride < R) part2 = a.skip_part[node_of(rn + stride)];
+      }
+      if (st == 3 || st == 4) {   // BaB: rows of partitions already decided / stopped are not bounded
+        btab[lane] = blo;
+        btab[64 + lane] = bhi;
+        __builtin_amdgcn_wave_barrier();
+        if (lane < FA_SYM_MAXC) {   // box values per column (0 on non-coefficient columns)
+          const int d = (lane >= 4 && lane - 4 < nc) ? cdim_s[lane - 4] : -1;
+          fa_sym_box_values(d >= 0 ? btab[max(d, 0)] : 0.f, d >= 0 ? btab[64 + max(d, 0)] : 0.f, bxv, lane);
+        }
+        float XA[NT][TMS][2][4], XB[NT][TMS][2][4];
+        // ---- layer-0 operands: identity forms (folded dims -> constant) + [hi | lo] interval rows;
+        //      L-block error columns negated
+#pragma unroll
+        for (int t = 0; t < TMS; ++t) {
+          if (t >= tin0) break;
+          // dims 16 t + 4 grp .. + 3 of the table (t < 4: n0 <= 64)
+          const float4 l4 = reinterpret_cast<const float4*>(btab)[(4 * t + grp) & 15];
+          const float4 h4 = reinterpret_cast<const float4*>(btab + 64)[(4 * t + grp) & 15];
+          const float xl4[4] = {l4.x, l4.y, l4.z, l4.w}, xh4[4] = {h4.x, h4.y, h4.z, h4.w};
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int k = 16 * t + 4 * grp + i;
+            const bool kv = k < n0;
+            const float xl = kv ? xl4[i] : 0.f, xh = kv ? xh4[i] : 0.f;
+            fa_sym_operand0<NT, CR>(xl, xh, kv, kv && ((cfg.fold >> k) & 1ull), k, g0, role, cdm, XA, t, i);
+          }
+        }
+        __builtin_amdgcn_wave_barrier();
+        fa_sym_layers_c<NT, TM, PAIR, PG, S, MASK>(std::make_integer_sequence<int, S::L>{}, net, a, cfg, smem, T, bxv,
+                                                   cdim_s, r, node, r, node, false, lane, XA, XB);
+        __builtin_amdgcn_wave_barrier();
+      }
+      blo = nlo;
+      bhi = nhi;
+      st = nst;
+      part1 = part2;
+      node = nnode;
+    }
+    return;
+  }
   for (int r0 = (blockIdx.x * nw + wave) * RPW; r0 < a.R; r0 += gridDim.x * nw * RPW) {
     const int r = __builtin_amdgcn_readfirstlane(r0);
     const bool v2 = PAIR && r + 1 < a.R;           // second row valid (else it shadows r, no writes)
@@ -656,19 +856,7 @@ fa_sym_kernel(NetDesc net, BoundArgs a, SymCfg cfg) {
       if (lane < FA_SYM_MAXC) {   // box values per column (0 on non-coefficient columns)
         float* bv = bxv + bi * SymSlab<NT>::BOX;
         const int d = (lane >= 4 && lane - 4 < nc) ? cdim_s[lane - 4] : -1;
-        const float l0 = d >= 0 ? bx.lo(d) : 0.f, h0 = d >= 0 ? bx.hi(d) : 0.f;
-        // centre / radius / magnitude of the column's range: exact for lattice boxes (integers
-        // below 2^22); any other range is enclosed outward ([mid - rad, mid + rad] contains it and
-        // m >= |mid| + rad), which keeps every bound sound
-        float mid = 0.5f * (l0 + h0), rad = 0.5f * (h0 - l0), mm = fmaxf(fabsf(l0), fabsf(h0));
-        const bool lattice = l0 == rintf(l0) && h0 == rintf(h0) && fabsf(l0) < 4194304.f && fabsf(h0) < 4194304.f;
-        if (!lattice) {
-          rad = nextafterf(fmaxf(h0 - mid, mid - l0), INFINITY);
-          mm = nextafterf(fabsf(mid) + rad, INFINITY);
-        }
-        bv[lane] = mid;
-        bv[FA_SYM_MAXC + lane] = rad;
-        bv[2 * FA_SYM_MAXC + lane] = mm;
+        fa_sym_box_values(d >= 0 ? bx.lo(d) : 0.f, d >= 0 ? bx.hi(d) : 0.f, bv, lane);
       }
       if (PG > 1 && lane < 32) {   // packed: the box's input ranges for the layer-0 operands
         const int d = lane & 15;
@@ -694,49 +882,54 @@ fa_sym_kernel(NetDesc net, BoundArgs a, SymCfg cfg) {
           xl = bt.lo(k);
           xh = bt.hi(k);
         }
-        const bool folded = kv && ((cfg.fold >> k) & 1ull);
-        const float m = fmaxf(fabsf(xl), fabsf(xh));
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct) {
-          float vu = 0.f, vl = 0.f;
-          if (kv) {
-            switch (role[ct]) {
-              // C/R kernels: (vu, vl) hold the centre / radius of the [upper | lower] operand pair
-              case 0: vu = (!folded && cdm[ct] == k) ? 1.f : 0.f; vl = CR ? 0.f : vu; break;
-              case 1: vu = folded ? xl : 0.f; vl = CR ? 0.f : vu; break;
-              case 2: vu = CR ? 0.f : g0 * m; vl = CR ? g0 * m : -vu; break;
-              case 3:
-                vu = CR ? 0.5f * (xh + xl) : xh;
-                vl = CR ? 0.5f * (xh - xl) : xl;
-                break;
-              case 4:
-                vu = CR ? 0.5f * g0 * (fabsf(xh) - fabsf(xl)) : g0 * fabsf(xh);
-                vl = CR ? 0.5f * g0 * (fabsf(xh) + fabsf(xl)) : -(g0 * fabsf(xl));
-                break;
-              default: break;
-            }
-          }
-          XA[ct][t][0][i] = vu;
-          XA[ct][t][1][i] = vl;
-        }
+        fa_sym_operand0<NT, CR>(xl, xh, kv, kv && ((cfg.fold >> k) & 1ull), k, g0, role, cdm, XA, t, i);
       }
     }
     __builtin_amdgcn_wave_barrier();
     if constexpr (S::L > 0) {
-      fa_sym_layers_c<NT, TM, PAIR, PG, S>(std::make_integer_sequence<int, S::L>{}, net, a, cfg, smem, T, bxv, cdim_s,
-                                           r, bx.node, rb, bxs[RPW - 1].node, v2, lane, XA, XB);
+      fa_sym_layers_c<NT, TM, PAIR, PG, S, MASK>(std::make_integer_sequence<int, S::L>{}, net, a, cfg, smem, T, bxv,
+                                                 cdim_s, r, bx.node, rb, bxs[RPW - 1].node, v2, lane, XA, XB);
     } else {
       for (int l = 0; l < net.n_layers; ++l) {
         if (l & 1)
-          fa_sym_layer<NT, TM, PAIR, PG>(net, a, cfg, smem, T, bxv, cdim_s, l, r, bx.node, rb, bxs[RPW - 1].node, v2,
-                                         lane, XB, XA);
+          fa_sym_layer<NT, TM, PAIR, PG, S, MASK>(net, a, cfg, smem, T, bxv, cdim_s, l, r, bx.node, rb,
+                                                  bxs[RPW - 1].node, v2, lane, XB, XA);
         else
-          fa_sym_layer<NT, TM, PAIR, PG>(net, a, cfg, smem, T, bxv, cdim_s, l, r, bx.node, rb, bxs[RPW - 1].node, v2,
-                                         lane, XA, XB);
+          fa_sym_layer<NT, TM, PAIR, PG, S, MASK>(net, a, cfg, smem, T, bxv, cdim_s, l, r, bx.node, rb,
+                                                  bxs[RPW - 1].node, v2, lane, XA, XB);
       }
     }
     __builtin_amdgcn_wave_barrier();
   }
+}
+
+template <int NT, int TM, bool PAIR, int PG = 1, class S = SymShapeAny>
+__global__ void __launch_bounds__((SymTune<NT, TM, PAIR, S>::THREADS))
+    __attribute__((amdgpu_waves_per_eu(SymTune<NT, TM, PAIR, S>::WPE))) fa_sym_kernel(NetDesc net, BoundArgs a, SymCfg cfg) {
+  constexpr int THREADS = SymTune<NT, TM, PAIR, S>::THREADS;
+  constexpr bool CL = S::L > 0 && PG == 1;   // compile-time layout of the staged block (SymLay)
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x;
+  const int stage_floats = CL ? SymLay<S>::STAGE : cfg.stage_floats;
+  const int lds_floats = CL ? SymLay<S>::LDS : cfg.lds_floats;
+  // ---- stage the MFMA-operand-order weights + biases (pre-permuted in `flat`; the block-diagonal
+  //      packed copy when PG > 1) into LDS
+  {
+    const float4* src = reinterpret_cast<const float4*>(a.flat + cfg.stage_off);
+    float4* dst = reinterpret_cast<float4*>(smem);
+    for (int e = tid; e < (stage_floats >> 2); e += THREADS) dst[e] = src[e];
+  }
+  int* cdim_s = reinterpret_cast<int*>(smem + lds_floats - FA_SYM_MAXC);
+  for (int c = tid; c < FA_SYM_MAXC; c += THREADS) cdim_s[c] = c < cfg.nc ? cfg.cdim[c] : -1;
+  __syncthreads();
+  // the mask-free row loop for launches that pass no mask (one uniform test per wave, not nine
+  // pointer tests per epilogue pass).  Only the unpaired shaped instances carry the second body and
+  // the prefetching loop: in the run-time-shape kernels they cost registers (the 3-column-tile one
+  // fell from 2 waves per SIMD to 1, the 7- and 10-tile ones gained 28-48 B/lane of scratch)
+  constexpr bool LEAN = S::L > 0 && !PAIR;
+  const bool masked = !LEAN || a.dead_in || a.dead_part || a.phase_in || a.dead_out;
+  if (masked) fa_sym_rows<NT, TM, PAIR, PG, S, true>(net, a, cfg, smem, cdim_s, lds_floats);
+  else fa_sym_rows<NT, TM, PAIR, PG, S, !LEAN>(net, a, cfg, smem, cdim_s, lds_floats);
 }
 
 // (A K-split variant with two waves per box -- each wave holding half of the K tiles and
@@ -838,12 +1031,38 @@ SymKernel select_kernel(int NT, int tmb) {
 
 constexpr int sym_key(int nt, int tm, bool pair, int pg) { return ((16 * nt + tm) * 2 + (pair ? 1 : 0)) * 8 + pg; }
 
+// A shaped instance and the check of its compile-time layout (SymLay) against the launch's tables.
+typedef bool (*SymLayoutOk)(const NetDesc&, const SymCfg&);
+struct SymInst {
+  SymKernel k = nullptr;
+  SymLayoutOk ok = nullptr;
+  int threads = 0, wpe = 0;   // SymTune of the instance
+  SymInst(std::nullptr_t = nullptr) {}
+  SymInst(SymKernel k_, SymLayoutOk ok_, int threads_, int wpe_) : k(k_), ok(ok_), threads(threads_), wpe(wpe_) {}
+};
+template <class S>
+bool sym_layout_ok(const NetDesc& net, const SymCfg& cfg);
+template <int NT, int TM, bool PAIR, int PG, class S>
+SymInst sym_inst() {
+  typedef SymTune<NT, TM, PAIR, S> Tune;
+  return SymInst(fa_sym_kernel<NT, TM, PAIR, PG, S>, sym_layout_ok<S>, Tune::THREADS, Tune::WPE);
+}
+template <class S>
+bool sym_layout_ok(const NetDesc& net, const SymCfg& cfg) {
+  for (int l = 0; l < S::L; ++l)
+    if (cfg.w_lds[l] != SymLay<S>::w(l) || cfg.b_lds[l] != SymLay<S>::b(l) || net.neuron_off[l] != SymLay<S>::noff(l))
+      return false;
+  return cfg.stage_floats == SymLay<S>::STAGE && cfg.lds_floats == SymLay<S>::LDS;
+}
+
 struct SymPick {
   SymKernel k;   // nullptr: the caller must use the LDS-tiled kernel
   int NT, tmb;
   bool pair;     // two box rows per wave (single-tile networks)
   int pg;        // packed: boxes per MFMA tile (1: not packed)
   bool shaped;
+  int threads, wpe;   // workgroup size; waves per SIMD the register limit is set for (SymTune)
+  int err;       // < 0: the staged block in `flat` does not have the layout the kernels expect
 };
 
 // The kernel a launch runs for this network and fold mask, and the column table of cfg, for
@@ -861,6 +1080,12 @@ SymPick pick_sym(const NetDesc& net, unsigned long long fold_mask, SymCfg& cfg) 
       cfg.cdim[nc++] = d;
     }
   cfg.nc = nc;
+  // the logit store derives a dim's coefficient column as d - #folded dims below d: the columns list
+  // the non-folded dims in increasing order, and no fold bit lies beyond the inputs
+  if (n0 < 64 && (fold_mask >> n0)) return p;
+  if (nc != n0 - __builtin_popcountll(fold_mask)) return p;
+  for (int c = 1; c < nc; ++c)
+    if (cfg.cdim[c] <= cfg.cdim[c - 1]) return p;
   const int cols = nc + 4;
   p.NT = (cols + 15) / 16;
   p.tmb = tm_bucket(p.NT, fa_widest_tiles(net, 0, net.n_layers));
@@ -871,19 +1096,73 @@ SymPick pick_sym(const NetDesc& net, unsigned long long fold_mask, SymCfg& cfg) 
   p.pg = (p.pair && net.pack_g > 1 && net.dims[0] <= 16 && use_pack()) ? net.pack_g : 1;
   if (p.pg > 1) k = select_packed(p.pg);
   if (!k) return p;
+  // LDS layout of the staged block
+  int off = 0;
+  if (p.pg > 1) {
+    cfg.w_lds[0] = 0;
+    off = p.pg * 256;
+    for (int l = 1; l < net.n_layers; ++l) {
+      cfg.w_lds[l] = off;
+      off += 256;
+    }
+    for (int l = 0; l < net.n_layers; ++l) {
+      cfg.b_lds[l] = off;
+      off += 16;
+    }
+    if (off != net.pack_floats) p.err = -1;     // layout mismatch with the packed block
+    cfg.stage_off = net.pack_off;
+  } else {
+    off = fa_lay_weights(net, net.n_layers, cfg.w_lds, 0);
+    off = fa_lay_biases(net, net.n_layers, cfg.b_lds, off);
+    off = ((off + 3) & ~3);
+    if (off != net.wperm_floats) p.err = -1;      // layout mismatch with the pre-permuted block
+    cfg.stage_off = net.wperm_off;
+  }
+  cfg.stage_floats = off;
+  cfg.lds_floats = off + FA_SYM_MAXC;           // + column -> input-dim table (ints)
+  p.threads = FA_SYM_THREADS(p.pair ? 1 : p.tmb);
+  p.wpe = FA_SYM_WAVES_PER_EU(p.NT, p.tmb, p.pair);
   // a compile-time-shape instance of the same (NT, TM, paired / packed) kernel, when there is one
   if (!fa_env_off("FAIRIFY_SYM_SHAPED")) {
 #define FA_SYM_ENTRY(NT, TM, PAIR, PG, ...) \
-  {sym_key(NT, TM, PAIR, PG), {__VA_ARGS__}, fa_sym_kernel<NT, TM, PAIR, PG, SymShape<__VA_ARGS__>>},
-    static const std::vector<FaShaped<SymKernel>> v = {FA_SYM_SHAPES(FA_SYM_ENTRY)};
+  {sym_key(NT, TM, PAIR, PG),                \
+   {__VA_ARGS__},                            \
+   sym_inst<NT, TM, PAIR, PG, SymShape<__VA_ARGS__>>()},
+    static const std::vector<FaShaped<SymInst>> v = {FA_SYM_SHAPES(FA_SYM_ENTRY)};
 #undef FA_SYM_ENTRY
-    if (const SymKernel ks = fa_find_shaped(v, net, sym_key(p.NT, p.tmb, p.pair, p.pg))) {
-      k = ks;
+    // the unpacked instances hold the layout as constants: one whose constants are not the launch's
+    // tables is not picked (the run-time-shape kernel reads the tables)
+    const SymInst si = fa_find_shaped(v, net, sym_key(p.NT, p.tmb, p.pair, p.pg));
+    if (si.k && !p.err && (p.pg > 1 || si.ok(net, cfg))) {
+      k = si.k;
       p.shaped = true;
+      p.threads = si.threads;
+      p.wpe = si.wpe;
     }
   }
   p.k = k;
   return p;
+}
+
+// workgroup size, dynamic LDS and box rows per workgroup of a pick
+struct SymGeom {
+  int threads, rows_per_block;
+  size_t bytes;
+};
+SymGeom sym_geom(const SymPick& p, const SymCfg& cfg) {
+  int slab = 0;
+  switch (p.NT) {
+    case 1:
+      slab = p.pg == 2 ? SymSlab<1, 2>::FLOATS : p.pg == 4 ? SymSlab<1, 4>::FLOATS : SymSlab<1>::FLOATS;
+      break;
+    case 2: slab = SymSlab<2>::FLOATS; break;
+    default: slab = SymSlab<3>::FLOATS; break;
+  }
+  SymGeom g;
+  g.threads = p.threads;
+  g.rows_per_block = (g.threads / 64) * (p.pair ? 2 * p.pg : 1);
+  g.bytes = (size_t)(cfg.lds_floats + (g.threads / 64) * slab) * sizeof(float);
+  return g;
 }
 
 }  // namespace
@@ -904,52 +1183,40 @@ extern "C" int fa_sym_try_launch(const NetDesc& net, BoundArgs a, unsigned long 
   const SymPick p = pick_sym(net, fold_mask, cfg);
   const SymKernel k = p.k;
   if (!k) return 0;
-  const int NT = p.NT, tmb = p.tmb, pg = p.pg;
-  const bool pair0 = p.pair;
-  int off = 0;
-  if (pg > 1) {
-    cfg.w_lds[0] = 0;
-    off = pg * 256;
-    for (int l = 1; l < net.n_layers; ++l) {
-      cfg.w_lds[l] = off;
-      off += 256;
-    }
-    for (int l = 0; l < net.n_layers; ++l) {
-      cfg.b_lds[l] = off;
-      off += 16;
-    }
-    if (off != net.pack_floats) return -1;      // layout mismatch with the packed block
-    cfg.stage_off = net.pack_off;
-  } else {
-    off = fa_lay_weights(net, net.n_layers, cfg.w_lds, 0);
-    off = fa_lay_biases(net, net.n_layers, cfg.b_lds, off);
-    off = ((off + 3) & ~3);
-    if (off != net.wperm_floats) return -1;       // layout mismatch with the pre-permuted block
-    cfg.stage_off = net.wperm_off;
-  }
-  cfg.stage_floats = off;
-  off += FA_SYM_MAXC;                           // + column -> input-dim table (ints)
-  cfg.lds_floats = off;
-  int slab = 0;
-  switch (NT) {
-    case 1:
-      slab = pg == 2 ? SymSlab<1, 2>::FLOATS : pg == 4 ? SymSlab<1, 4>::FLOATS : SymSlab<1>::FLOATS;
-      break;
-    case 2: slab = SymSlab<2>::FLOATS; break;
-    default: slab = SymSlab<3>::FLOATS; break;
-  }
-  const int threads = (!pair0 && NT == 1 && tmb == 7) ? FA_SYM_BIG_THREADS : FA_THREADS;   // = FA_SYM_THREADS(TM)
-  const int rows_per_block = (threads / 64) * (pair0 ? 2 * pg : 1);
-  const size_t bytes = (size_t)(off + (threads / 64) * slab) * sizeof(float);
-  if (bytes > 160 * 1024) return 0;
-  const int per_cu = fa_blocks_per_cu((const void*)k, threads, bytes);
+  if (p.err) return p.err;
+  const SymGeom g = sym_geom(p, cfg);
+  if (g.bytes > 160 * 1024) return 0;
+  const int per_cu = fa_blocks_per_cu((const void*)k, g.threads, g.bytes);
   if (!per_cu) return -4;
-  long long blocks = (a.R + rows_per_block - 1) / rows_per_block;
+  long long blocks = (a.R + g.rows_per_block - 1) / g.rows_per_block;
   const long long cap = (long long)fa_device_cus() * per_cu;
   if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(threads), bytes, stream, net, a, cfg);
+  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(g.threads), g.bytes, stream, net, a, cfg);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 1 : -(int)e;
+}
+
+// The geometry fa_sym_try_launch uses for this network and fold mask: out = {threads per workgroup,
+// dynamic LDS bytes, resident workgroups per CU, CUs, box rows per workgroup, waves per SIMD the
+// kernel's register limit is set for, shaped, registers per lane the runtime reports (0: unknown)}.  1 when the register-resident kernel would run, else 0.
+extern "C" int fa_sym_geometry(const NetDesc& net, unsigned long long fold_mask, int* out) {
+  SymCfg cfg{};
+  const SymPick p = pick_sym(net, fold_mask, cfg);
+  if (!p.k || p.err) return 0;
+  const SymGeom g = sym_geom(p, cfg);
+  if (g.bytes > 160 * 1024) return 0;
+  const int per_cu = fa_blocks_per_cu((const void*)p.k, g.threads, g.bytes);
+  if (!per_cu) return 0;
+  out[0] = g.threads;
+  out[1] = (int)g.bytes;
+  out[2] = per_cu;
+  out[3] = fa_device_cus();
+  out[4] = g.rows_per_block;
+  out[5] = p.wpe;
+  out[6] = p.shaped;
+  hipFuncAttributes fa{};
+  out[7] = hipFuncGetAttributes(&fa, (const void*)p.k) == hipSuccess ? fa.numRegs : 0;
+  return 1;
 }
 
 #define FA_SYM_LDS(NT, TM) FA_LDS_K((sym_ptr<NT, TM>())),

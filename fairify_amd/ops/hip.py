@@ -68,12 +68,13 @@ def _ptrs(**tensors) -> dict:
     return {k: t.data_ptr() for k, t in tensors.items() if t is not None}
 
 
-def _bound_kw(be, lo, hi, dead=None, res=None, layer_lb=None, layer_ub=None):
+def _bound_kw(be, lo, hi, dead=None, res=None, layer_lb=None, layer_ub=None, rows=None):
     """The block the bound-family bindings share: ``(keywords, tensors)`` -- row boxes, forced-dead
     mask, ``res``'s logit bounds and forms, layer bounds, R and the stream.  The checked contiguous
     ``tensors`` (same keys) must stay alive until the launch is enqueued."""
-    R, n0 = lo.shape
-    t = dict(flat=be.flat, lo=_c(lo, torch.float32, (R, n0), "lo"), hi=_c(hi, torch.float32, (R, n0), "hi"),
+    B, n0 = lo.shape
+    R = B if rows is None else rows       # rows: node-row expansion, R = V rows per box
+    t = dict(flat=be.flat, lo=_c(lo, torch.float32, (B, n0), "lo"), hi=_c(hi, torch.float32, (B, n0), "hi"),
              dead_in=None if dead is None else _c(dead, torch.uint8, (R, be.n_hidden), "dead"),
              layer_lb=layer_lb, layer_ub=layer_ub)
     if res is not None:
@@ -208,37 +209,69 @@ def point_bounds(be, x: torch.Tensor, dead: Optional[torch.Tensor] = None):
 # ------------------------------------------------------------------------------------------------
 def bounds(be, lo: torch.Tensor, hi: torch.Tensor, mode: str = "symbolic", dead: Optional[torch.Tensor] = None,
            keep_layers: bool = False, G: int = 0, fold: Sequence[int] = (),
-           phase: Optional[torch.Tensor] = None) -> ref.BoundResult:
+           phase: Optional[torch.Tensor] = None, *, dead_out: bool = True, V: int = 0, pa: Sequence[int] = (),
+           values: Optional[torch.Tensor] = None, skip_status: Optional[torch.Tensor] = None,
+           skip_part: Optional[torch.Tensor] = None, fill: Optional[float] = None) -> ref.BoundResult:
     """``fold``: input dims with lo == hi in EVERY row (folded into the constant column of the
-    register-resident symbolic kernel; the caller guarantees degeneracy)."""
+    register-resident symbolic kernel; the caller guarantees degeneracy).
+
+    The keyword-only arguments give tests the launch form of the native BaB runtimes:
+    ``dead_out=False`` passes no stable-inactive output (with no ``dead`` / ``phase``: a launch
+    without any mask); ``V`` > 0 with ``pa`` and ``values`` [V, len(pa)] float32 expands every box
+    of ``lo`` / ``hi`` into V rows whose PA dims take ``values[r % V]``; ``skip_status`` int8 [P] and
+    ``skip_part`` int32 [boxes] skip the rows of partitions whose status is neither 3 nor 4;
+    ``fill`` pre-fills every float output with a sentinel (0xEE for the byte outputs): skipped rows
+    keep it."""
     R, n0 = lo.shape
     if n0 != be.n0:
         raise ValueError(f"box width {n0} != network input {be.n0}")
+    if V < 0 or (V > 0 and (values is None or not len(pa))):
+        raise ValueError("bounds: V > 0 needs pa and values [V, len(pa)]")
+    if (skip_status is None) != (skip_part is None):
+        raise ValueError("bounds: skip_status and skip_part go together")
+    if V > 0:
+        R *= V
     dev = lo.device
     sym = 1 if mode == "symbolic" else 0
     f32 = dict(dtype=torch.float32, device=dev)
-    res = ref.BoundResult(out_lb=torch.empty(R, **f32), out_ub=torch.empty(R, **f32))
+
+    def new(*shape, dtype=torch.float32):
+        if fill is None:
+            return torch.empty(*shape, dtype=dtype, device=dev)
+        return torch.full(shape, fill if dtype.is_floating_point else 0xEE, dtype=dtype, device=dev)
+
+    res = ref.BoundResult(out_lb=new(R), out_ub=new(R))
     if sym:
-        res.Lc = torch.empty(R, n0, **f32)
-        res.L0 = torch.empty(R, **f32)
-        res.Le = torch.empty(R, **f32)
-        res.Uc = torch.empty(R, n0, **f32)
-        res.U0 = torch.empty(R, **f32)
-        res.Ue = torch.empty(R, **f32)
+        res.Lc = new(R, n0)
+        res.L0 = new(R)
+        res.Le = new(R)
+        res.Uc = new(R, n0)
+        res.U0 = new(R)
+        res.Ue = new(R)
     N = be.mlp.n_neurons
     lay_lb = lay_ub = None
     if keep_layers:
-        lay_lb = torch.empty(R, N, **f32)
-        lay_ub = torch.empty(R, N, **f32)
-    dead_out = torch.empty(R, be.n_hidden, dtype=torch.uint8, device=dev) if be.n_hidden else None
+        lay_lb = new(R, N)
+        lay_ub = new(R, N)
+    dead_out = new(R, be.n_hidden, dtype=torch.uint8) if be.n_hidden and dead_out else None
     ph = infeas = None
     if phase is not None:
         ph = _c(phase, torch.int8, (R, be.n_hidden), "phase")
         infeas = torch.zeros(R, dtype=torch.uint8, device=dev)
-    kw, _keep = _bound_kw(be, lo, hi, dead, res, lay_lb, lay_ub)
+    kw, _keep = _bound_kw(be, lo, hi, dead, res, lay_lb, lay_ub, rows=R)
+    bab = {}
+    if V > 0:
+        vals = _c(values, torch.float32, (V, len(pa)), "values")
+        bab.update(V=V, pa=[int(d) for d in pa], values=vals.data_ptr())
+    if skip_status is not None:
+        st = _c(skip_status, torch.int8, None, "skip_status")
+        sp = _c(skip_part, torch.int32, (lo.shape[0],), "skip_part")
+        if st.dim() != 1 or (sp.numel() and (int(sp.min()) < 0 or int(sp.max()) >= st.shape[0])):
+            raise ValueError("bounds: skip_part indexes outside skip_status")
+        bab.update(skip_status=st.data_ptr(), skip_part=sp.data_ptr())
     if R:
         ext().bounds(_net(be), **kw, **_ptrs(dead_out=dead_out, phase_in=ph, infeas=infeas), symbolic=sym, G=G,
-                     fold=_fold_mask(fold, n0))
+                     fold=_fold_mask(fold, n0), **bab)
     if infeas is not None:
         res.infeasible = infeas.bool()
     if keep_layers:

@@ -39,11 +39,14 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--json-out", default=None)
     ap.add_argument("--no-fold", action="store_true", help="do not fix/fold the protected attribute")
+    ap.add_argument("--no-mask", action="store_true",
+                    help="symbolic mode: pass no dead_out either (the mask-free launch of the BaB runtimes)")
     args = ap.parse_args()
     import torch
 
     from fairify_amd import presets
     from fairify_amd.models.zoo import get_model
+    from fairify_amd.ops import hip as hip_ops
     from fairify_amd.ops.backend import Backend
 
     dev = torch.device("cuda")
@@ -68,6 +71,8 @@ def main():
         def run():
             if args.mode == "points":
                 be.point_bounds(lo)
+            elif args.no_mask:
+                hip_ops.bounds(be, lo, hi, mode=args.mode, fold=fold, dead_out=False)
             else:
                 be.bounds(lo, hi, mode=args.mode, fold=fold)
 
@@ -82,7 +87,7 @@ def main():
         dims = [m.n_in] + m.widths
         fl = gemm_flops(dims, args.rows, args.mode == "symbolic") if args.mode != "points" else \
             sum(2 * 2 * dims[l] * dims[l + 1] for l in range(len(dims) - 1)) * args.rows
-        row = dict(model=name, dims=dims, rows=args.rows, mode=args.mode, ms=round(dt * 1e3, 4),
+        row = dict(model=name, dims=dims, rows=args.rows, mode=args.mode + ("-nomask" if args.no_mask else ""), ms=round(dt * 1e3, 4),
                    mrows_per_s=round(args.rows / dt / 1e6, 3), gemm_tflops=round(fl / dt / 1e12, 2))
         out.append(row)
         print(json.dumps(row), flush=True)
