@@ -7,6 +7,7 @@
     python -m fairify_amd.cli analyze --preset experiment/AC-3 --model AC-3 --fairer AC-3 ...
     python -m fairify_amd.cli measure --preset src/GC-age --model GC-1 --results results/gc --out results/gc-rate
     python -m fairify_amd.cli measure --preset src/GC-age --model GC-1 --certify [--node-budget N] [--leaf-points K]
+    python -m fairify_amd.cli audit --preset src/AC-sex --model AC-3 [--data rows.csv] [--results results/ac] --out ...
     python -m fairify_amd.cli repair --model AC-3 --counterexamples results/ac3/counterexamples.csv ...
     python -m fairify_amd.cli export-cex --preset src/AC-sex --model AC-3 --results results/ac
 
@@ -109,6 +110,15 @@ def cmd_measure(args):
                          max_partitions=args.max_partitions, check_unsat=args.check_unsat, weights=args.weights,
                          device=_device(args.device), out_dir=args.out, certify=args.certify,
                          node_budget=args.node_budget, leaf_points=args.leaf_points)
+    print(json.dumps(out, indent=2, default=float))
+
+
+def cmd_audit(args):
+    from .analysis.audit import audit_preset
+
+    out = audit_preset(args.preset, args.model, data=args.data, split=args.split, results=args.results,
+                       weights=args.weights, seed=args.seed, device=_device(args.device), max_rows=args.max_rows,
+                       out_dir=args.out, pairs_out=args.pairs_out)
     print(json.dumps(out, indent=2, default=float))
 
 
@@ -274,6 +284,25 @@ def main(argv=None):
                     help="--certify: open nodes of at most this many points are enumerated (<= 65536)")
     ms.add_argument("--out", default=None, help="directory for rate.csv / rate.json (and bounds.csv)")
     ms.set_defaults(fn=cmd_measure)
+
+    au = sub.add_parser("audit", help="exact per-row discrimination flags of a table of individuals")
+    au.add_argument("--preset", required=True)
+    au.add_argument("--model", required=True)
+    au.add_argument("--data", default=None,
+                    help="CSV of encoded integer rows whose header holds the domain's feature names "
+                         "(default: the suite's dataset)")
+    au.add_argument("--split", default="all", choices=["all", "train", "test"], help="without --data: which rows")
+    au.add_argument("--results", default=None,
+                    help="results dir of a verify run: rows per verdict class; a flagged row inside an UNSAT "
+                         "partition is a prover bug (SoundnessError)")
+    au.add_argument("--max-rows", type=int, default=None)
+    au.add_argument("--pairs-out", default=None,
+                    help="FILE.npz: one exactly confirmed pair (x, xp) per flagged row, for repair --counterexamples")
+    au.add_argument("--seed", type=int, default=0)
+    au.add_argument("--weights", default="zoo")
+    au.add_argument("--device", default=None)
+    au.add_argument("--out", default=None, help="directory for audit.csv / audit.json")
+    au.set_defaults(fn=cmd_audit)
 
     r = sub.add_parser("repair", help="bias localisation + masked fine-tune / counterexample retraining")
     r.add_argument("--model", required=True)

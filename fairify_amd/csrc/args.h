@@ -605,3 +605,27 @@ struct CountArgs {
   int leaf_cap;
   int* counters;            // [0] children, [1] leaves, [2] nodes that did not fit (must stay 0)
 };
+
+// Audit of real individuals (csrc/audit.hip, definitions in ops/audit.py): one row per individual from
+// HBM, forwarded once; every counterpart (PA := values[v'], RA += offset vector e) streams through the
+// same rigorous point forward and sets bit v' of the row's cert / poss masks.  No atomics.
+struct AuditArgs {
+  const float* flat;
+  const float* x;           // [N, n0] integral rows
+  const int* own;           // [N] index of the row's PA coordinates in values, -1: outside the PA domain
+  int N;
+  int V;                    // PA assignments of the whole PA domain
+  int npa;
+  int pa_idx[FA_MAX_PA];
+  const int64_t* values;    // [V, npa]
+  int Pp;                   // valid ordered pairs
+  const int64_t* pairs;     // [Pp, 2]
+  int nra;                  // 0: PA-only query
+  int ra_idx[FA_MAX_RA];
+  int tau;
+  int E;                    // (2 tau + 1)^nra offset vectors, row-major over ra_idx (1 when nra == 0)
+  int* cert;                // [N] bit v': some e certainly flips
+  int* poss;                // [N] bit v': some e possibly flips
+  int8_t* own_sign;         // [N] -1: u < 0, +1: l > 0, else 0
+  int blocks;               // workgroups (64-row passes strided over them)
+};

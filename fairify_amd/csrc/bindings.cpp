@@ -36,6 +36,7 @@ extern "C" int fa_sym_geometry(const NetDesc& net, unsigned long long fold_mask,
 extern "C" int fa_crown_shaped(const NetDesc& net, int mask);
 extern "C" int fa_refine_shaped(const NetDesc& net, int logit);
 extern "C" int fa_rate_launch(const NetDesc& net, RateArgs a, hipStream_t stream);
+extern "C" int fa_audit_launch(const NetDesc& net, AuditArgs a, hipStream_t stream);
 extern "C" int fa_count_enum_launch(const NetDesc& net, EnumArgs a, hipStream_t stream);
 extern "C" int fa_count_rows_launch(CountArgs a, hipStream_t stream);
 extern "C" int fa_count_level_launch(CountArgs a, hipStream_t stream);
@@ -444,6 +445,40 @@ PYBIND11_MODULE(_C, m) {
     const int rc = fa_rate_launch(net.d, a, finish(k));
     if (rc == -3) throw std::invalid_argument("rate: shape not covered (layer > 160, inputs > 32, V > 32 or E > 32)");
     ckl(rc, "rate");
+  });
+
+  // audit of real rows (csrc/audit.hip): per-row cert / poss masks and the own sign.  Returns false when
+  // the kernel does not cover the shape (the caller takes the composed path), true when launched
+  m.def("audit", [](const Net& net, py::kwargs kw) {
+    Kw k("audit", kw);
+    AuditArgs a{};
+    a.flat = k.need<const float>("flat");
+    a.x = k.need<const float>("x");
+    a.own = k.need<const int>("own");
+    a.N = k.i("N");
+    a.V = k.i("V");
+    a.npa = dims(k, "pa", a.pa_idx, FA_MAX_PA, "too many PA/RA dims");
+    a.values = k.need<const int64_t>("values");
+    a.Pp = k.i("Pp");
+    a.pairs = k.ptr<const int64_t>("pairs");
+    a.nra = dims(k, "ra", a.ra_idx, FA_MAX_RA, "too many PA/RA dims");
+    a.tau = k.i("tau");
+    a.E = k.i("E");
+    a.cert = k.need<int>("cert");
+    a.poss = k.need<int>("poss");
+    a.own_sign = k.need<int8_t>("own_sign");
+    a.blocks = k.i("blocks");
+    if (a.N < 0) throw std::invalid_argument("audit: negative row count");
+    if (a.Pp > 0 && !a.pairs) throw py::type_error("audit() missing required keyword argument 'pairs'");
+    for (int q = 0; q < a.npa; ++q)
+      if (a.pa_idx[q] < 0 || a.pa_idx[q] >= net.d.dims[0]) throw std::invalid_argument("audit: PA dim outside the inputs");
+    for (int q = 0; q < a.nra; ++q)
+      if (a.ra_idx[q] < 0 || a.ra_idx[q] >= net.d.dims[0]) throw std::invalid_argument("audit: RA dim outside the inputs");
+    const int rc = fa_audit_launch(net.d, a, finish(k));
+    if (rc == -3) return false;
+    if (rc == -2) throw std::invalid_argument("audit: workgroup count outside 1..number of 64-row passes");
+    ckl(rc, "audit");
+    return true;
   });
 
   // counting branch-and-bound (csrc/count.hip).  count_enum: leaf enumeration; amb zero-initialised by

@@ -634,6 +634,66 @@ def rate_counts(be, q, lo, hi, pids, n_samples, seed, values, pairs, split: Opti
     return flips, amb, idx
 
 
+_AUDIT_BLOCKS = 1024     # workgroups a long table of rows is walked by (4 per CU); W is staged once each
+
+
+def audit_passes(N: int) -> int:
+    """64-row passes of ``fa_audit_kernel``: the largest workgroup count."""
+    return max(1, (int(N) + 63) // 64)
+
+
+def audit_masks(be, q, X, own, values, pairs, blocks: Optional[int] = None):
+    """Per-row audit masks of rows ``X`` [N, n0] in one fused launch (``fa_audit_kernel``, definitions
+    in ops/audit.py): (cert int32 [N], poss int32 [N], own_sign int8 [N]), or ``None`` when the kernel
+    does not cover the shape (a layer over 160 wide, over 32 inputs, more than 64 KB of LDS): the
+    caller takes ``ops/audit.audit_masks_ref``.  ``blocks``: workgroups (default: one per 64-row
+    pass, at most 1 024); every value gives the same outputs."""
+    from .audit import MAX_VALUES
+    from .rate import MAX_OFFSETS, offset_vectors
+
+    if X.dim() != 2 or X.shape[1] != be.n0:
+        raise ValueError(f"X: expected [N, {be.n0}], got {tuple(X.shape)}")
+    N = int(X.shape[0])
+    dev = X.device
+    npa = len(q.pa_idx)
+    if values.dim() != 2 or values.shape[1] != npa:
+        raise ValueError(f"values: expected [V, {npa}], got {tuple(values.shape)}")
+    V, Pp = int(values.shape[0]), int(pairs.shape[0])
+    if not 1 <= V <= MAX_VALUES:
+        raise ValueError(f"audit: {V} PA assignments, the kernel covers 1..{MAX_VALUES}")
+    X = _c(X, torch.float32, (N, be.n0), "X")
+    own = _c(own, torch.int32, (N,), "own")
+    values = _c(values, torch.int64, (V, npa), "values")
+    pairs = _c(pairs, torch.int64, (Pp, 2), "pairs")
+    if any(t.device != dev for t in (own, values, pairs, be.flat)):
+        raise ValueError("audit: X, own, values, pairs and the network must be on one device")
+    if Pp and (int(pairs.min()) < 0 or int(pairs.max()) >= V):
+        raise ValueError("pairs: index outside [0, V)")
+    if N:
+        omin, omax = torch.stack(torch.aminmax(own)).tolist()           # one read-back
+        if omin < -1 or omax >= V:
+            raise ValueError("own: index outside [-1, V)")
+    E = int(offset_vectors(q).shape[0])                    # raises over MAX_OFFSETS
+    assert E <= MAX_OFFSETS
+    if blocks is None:
+        blocks = min(audit_passes(N), _AUDIT_BLOCKS)
+    if not 1 <= int(blocks) <= audit_passes(N):
+        raise ValueError(f"audit: {blocks} workgroups outside 1..{audit_passes(N)}")
+    cert = torch.zeros(N, dtype=torch.int32, device=dev)
+    poss = torch.zeros(N, dtype=torch.int32, device=dev)
+    sign = torch.zeros(N, dtype=torch.int8, device=dev)
+    if max([be.n0] + list(be.widths)) > 160 or be.n0 > 32:
+        return None
+    if N:
+        ok = ext().audit(_net(be), **_ptrs(flat=be.flat, x=X, own=own, values=values, pairs=pairs if Pp else None,
+                                           cert=cert, poss=poss, own_sign=sign),
+                         N=N, V=V, pa=list(q.pa_idx), Pp=Pp, ra=list(q.ra_idx) if q.relaxed else [],
+                         tau=int(q.tau) if q.relaxed else 0, E=E, blocks=int(blocks), stream=_stream(dev))
+        if not ok:
+            return None
+    return cert, poss, sign
+
+
 # Workgroups of a leaf list: at least 1 024 (4 per CU), and enough that a workgroup enumerates about
 # _ENUM_POINTS points per staging of W -- leaves of 1 000 points measured 4 - 13 % faster one per
 # workgroup than eight per workgroup (profiles/r12/count/README.md); only small leaves share a workgroup
