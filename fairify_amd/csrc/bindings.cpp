@@ -69,6 +69,14 @@ extern "C" int fa_actdiff_launch(const NetDesc& net, const float* flat, const fl
 extern "C" int fa_pack_masks_launch(const uint8_t* src, int P, int N, int stride, int sel, uint8_t* out, int NB,
                                     unsigned long long* hash, hipStream_t stream);
 
+// BaB level kernels (bab.hip), bound one launch at a time for the level tests
+extern "C" int fa_split_launch(SplitArgs a, hipStream_t stream);
+extern "C" int fa_settle_launch(SettleArgs s, hipStream_t stream);
+extern "C" int fa_bab_init_launch(BabInitArgs a, hipStream_t stream);
+extern "C" int fa_bab_finish_launch(int P, const int8_t* status, const int* nodes, const int* open_left, int* out,
+                                    hipStream_t stream);
+extern "C" int fa_mark_unknown_launch(const int* part, int n, int8_t* status, hipStream_t stream);
+
 template <typename T>
 static T* P(uintptr_t p) { return reinterpret_cast<T*>(p); }
 
@@ -275,6 +283,41 @@ static BetaArgs beta_args(const Net& net, Kw& k) {
   if ((net.d.dims[0] < 64 && (a.ramask >> net.d.dims[0])) || (a.ramask && (!a.plo || !a.phi)))
     throw std::invalid_argument("beta_level: RA mask beyond the inputs or no x' box");
   return a;
+}
+
+// Level end (SettleArgs): the keys are the field names behind `pre` ("" for the settle binding,
+// "settle_" for the block fused into a split launch); esc goes as the two lists esc_budget / esc_open
+// (esc.n = their length).  `fused`: the workgroup counter `done` is needed too.
+static SettleArgs settle_args(Kw& k, const std::string& fn, const std::string& pre, bool fused) {
+  // Kw keeps the key's characters only for the call: the composed names live here
+  std::vector<std::string> names;
+  names.reserve(20);
+  auto key = [&](const char* f) { names.push_back(pre + f); return names.back().c_str(); };
+  SettleArgs s{};
+  s.P = k.i(key("P"));
+  if (s.P <= 0) throw std::invalid_argument(fn + ": " + pre + "P must be positive");
+  s.status = k.need<int8_t>(key("status"));
+  s.lvl_open = k.need<int>(key("lvl_open"));
+  s.part_open = k.ptr<int>(key("part_open"));
+  s.part_nodes = k.need<const int>(key("part_nodes"));
+  s.nodes_start = k.need<int>(key("nodes_start"));
+  s.prev_start = k.need<int>(key("prev_start"));
+  s.counters_cur = k.need<const int>(key("counters_cur"));
+  s.counters_next = k.need<int>(key("counters_next"));
+  s.host_counts = k.need<int>(key("host_counts"));
+  s.pbudget = k.ptr<int>(key("pbudget"));
+  s.prob = k.ptr<uint8_t>(key("prob"));
+  s.budget2 = k.i(key("budget2"));
+  s.max_open = k.i(key("max_open"));
+  const std::vector<int> eb = k.ints(key("esc_budget")), eo = k.ints(key("esc_open"));
+  if (eb.size() != eo.size() || eb.size() > FA_MAX_ESC)
+    throw std::invalid_argument(fn + ": esc_budget / esc_open hold the same number of steps, at most 4");
+  s.esc.n = (int)eb.size();
+  std::copy(eb.begin(), eb.end(), s.esc.budget);
+  std::copy(eo.begin(), eo.end(), s.esc.open);
+  s.done = fused ? k.need<int>(key("done")) : k.ptr<int>(key("done"));
+  if (s.prob && !s.pbudget) throw std::invalid_argument(fn + ": prob without pbudget");
+  return s;
 }
 
 PYBIND11_MODULE(_C, m) {
@@ -661,6 +704,122 @@ PYBIND11_MODULE(_C, m) {
     if (a.smear && (!a.lay_lb || !a.lay_ub || !a.W0T || a.n1 <= 0 || a.lay_N < a.n1))
       throw std::invalid_argument("certify: smear needs lay_lb, lay_ub, W0T and 0 < n1 <= lay_N");
     ckl(fa_certify_launch(a, finish(k)), "certify");
+  });
+
+  // ---- BaB level kernels (bab.hip), one launch each: what tests/test_split_level_gpu.py compares with
+  // the plain oracle of tests/split_cases.py.  The native runtime (bab_runtime.cpp) fills the same
+  // structs itself.
+  // split_level: one sub-batch of a level.  The settle_* keys (the SettleArgs fields) fuse the level
+  // end into this launch; without settle_P there is none (settle.P = 0).  host_counts may be device
+  // memory.
+  m.def("split_level", [](py::kwargs kw) {
+    Kw k("split_level", kw);
+    SplitArgs a{};
+    a.Nn = k.i("Nn"); a.n0 = k.i("n0"); a.relaxed = k.i("relaxed");
+    a.V = k.i("V"); a.Pp = k.i("Pp"); a.norient = k.i("norient");
+    a.nra = dims(k, "ra", a.ra_idx, FA_MAX_RA, "too many PA/RA dims");
+    a.tau = k.f("tau");
+    auto opt_if = [&](const char* key, bool req) { return req ? k.need<float>(key) : k.ptr<float>(key); };
+    a.xlo = k.need<const float>("xlo"); a.xhi = k.need<const float>("xhi");
+    a.xplo = opt_if("xplo", a.relaxed); a.xphi = opt_if("xphi", a.relaxed);
+    a.part = k.need<const int>("part");
+    a.open = k.need<const uint8_t>("open");
+    a.leaf = k.need<const uint8_t>("leaf");
+    a.scores = k.need<const float>("scores");
+    a.cand_x = k.need<const float>("cand_x"); a.cand_xp = k.need<const float>("cand_xp");
+    a.pe_lb = k.need<const float>("pe_lb"); a.pe_ub = k.need<const float>("pe_ub");
+    a.olb = k.need<const float>("olb"); a.oub = k.need<const float>("oub");
+    a.olbp = k.need<const float>("olbp"); a.oubp = k.need<const float>("oubp");
+    a.pairs = k.ptr<const int64_t>("pairs");
+    a.values = k.ptr<const int64_t>("values");
+    a.npa = dims(k, "pa", a.pa_idx, FA_CMAX_PA, "too many PA/RA dims");
+    a.shared = a.relaxed ? k.need<const uint8_t>("shared") : k.ptr<const uint8_t>("shared");
+    a.status = k.need<int8_t>("status");
+    a.part_nodes = k.need<int>("part_nodes");
+    a.part_open = k.ptr<int>("part_open");
+    a.lvl_open = k.ptr<int>("lvl_open");
+    a.nodes_start = k.need<const int>("nodes_start");
+    a.prev_start = k.need<const int>("prev_start");
+    a.budget = k.i("budget");
+    a.pbudget = k.ptr<const int>("pbudget");
+    a.prob = k.ptr<uint8_t>("prob");
+    a.budget2 = k.i("budget2");
+    a.m = k.i("m");
+    a.target = k.i("target");
+    a.oxlo = k.need<float>("oxlo"); a.oxhi = k.need<float>("oxhi");
+    a.oxplo = opt_if("oxplo", a.relaxed); a.oxphi = opt_if("oxphi", a.relaxed);
+    a.opart = k.need<int>("opart");
+    a.count_out = k.need<int>("count_out");
+    a.cap = k.i("cap");
+    a.cand_buf = k.need<float>("cand_buf");
+    a.cand_count = k.need<int>("cand_count");
+    a.cand_cap = k.i("cand_cap");
+    if (kw.contains("settle_P")) a.settle = settle_args(k, "split_level", "settle_", true);
+    if (a.Nn < 0 || a.n0 < 1 || a.V < 1 || a.norient < 1 || a.norient > 2 || a.Pp < 0 || a.cap < 0 || a.cand_cap < 0)
+      throw std::invalid_argument("split_level: sizes out of range");
+    if ((a.Pp > 0 && !a.pairs) || (a.npa > 0 && !a.values))
+      throw py::type_error("split_level() missing required keyword argument 'pairs' / 'values'");
+    for (int q = 0; q < a.npa; ++q)
+      if (a.pa_idx[q] < 0 || a.pa_idx[q] >= a.n0) throw std::invalid_argument("split_level: PA dim outside the inputs");
+    for (int q = 0; q < a.nra; ++q)
+      if (a.ra_idx[q] < 0 || a.ra_idx[q] >= a.n0) throw std::invalid_argument("split_level: RA dim outside the inputs");
+    const int rc = fa_split_launch(a, finish(k));
+    if (rc == -3) throw std::invalid_argument("split_level: shape not covered (n0 > 64, more than 8 PA or RA dims)");
+    ckl(rc, "split_level");
+  });
+  m.def("settle", [](py::kwargs kw) {
+    Kw k("settle", kw);
+    const SettleArgs s = settle_args(k, "settle", "", false);
+    ckl(fa_settle_launch(s, finish(k)), "settle");
+  });
+  // stage: the device copy of the staged block [status int8 x P, padded to 4 B | running partition
+  // ids x n_run | lo x n_run*n0 | hi x n_run*n0] (uint8)
+  m.def("bab_init", [](py::kwargs kw) {
+    Kw k("bab_init", kw);
+    BabInitArgs a{};
+    a.P = k.i("P"); a.n_run = k.i("n_run"); a.n0 = k.i("n0");
+    a.stage = k.need<const unsigned char>("stage");
+    a.status = k.need<int8_t>("status");
+    a.nodes = k.need<int>("nodes"); a.open_left = k.need<int>("open_left"); a.lvl_open = k.need<int>("lvl_open");
+    a.nodes_start = k.need<int>("nodes_start"); a.prev_start = k.need<int>("prev_start");
+    a.part = k.need<int>("part");
+    a.xlo = k.need<float>("xlo"); a.xhi = k.need<float>("xhi");
+    a.xplo = k.ptr<float>("xplo"); a.xphi = k.ptr<float>("xphi");
+    a.nra = dims(k, "ra", a.ra_idx, FA_MAX_RA, "too many PA/RA dims");
+    a.tau = k.f("tau");
+    a.counters = k.need<int>("counters");
+    a.pbudget = k.ptr<int>("pbudget");
+    a.prob = k.ptr<uint8_t>("prob");
+    a.budget = k.i("budget");
+    if (a.P < 0 || a.n_run < 0 || a.n0 < 1) throw std::invalid_argument("bab_init: sizes out of range");
+    if ((a.xplo == nullptr) != (a.xphi == nullptr)) throw std::invalid_argument("bab_init: xplo and xphi go together");
+    const int rc = fa_bab_init_launch(a, finish(k));
+    if (rc == -3) throw std::invalid_argument("bab_init: more than 8 RA dims");
+    ckl(rc, "bab_init");
+  });
+  m.def("bab_finish", [](py::kwargs kw) {
+    Kw k("bab_finish", kw);
+    const int Pn = k.i("P");
+    const int8_t* status = k.need<const int8_t>("status");
+    const int* nodes = k.need<const int>("nodes");
+    const int* open_left = k.need<const int>("open_left");
+    int* out = k.need<int>("out");
+    ckl(fa_bab_finish_launch(Pn, status, nodes, open_left, out, finish(k)), "bab_finish");
+  });
+  m.def("mark_unknown", [](py::kwargs kw) {
+    Kw k("mark_unknown", kw);
+    const int* part = k.need<const int>("part");
+    const int n = k.i("n");
+    int8_t* status = k.need<int8_t>("status");
+    ckl(fa_mark_unknown_launch(part, n, status, finish(k)), "mark_unknown");
+  });
+  m.def("set_status", [](py::kwargs kw) {
+    Kw k("set_status", kw);
+    const int* idx = k.need<const int>("idx");
+    const int n = k.i("n");
+    int8_t* status = k.need<int8_t>("status");
+    const int v = k.i("v");
+    ckl(fa_set_status_launch(idx, n, status, (int8_t)v, finish(k)), "set_status");
   });
 
   m.def("decode", [](std::vector<int> radix, std::vector<long long> div, std::vector<int> chunk_off,

@@ -484,6 +484,251 @@ def pair_certify(be, res_x, res_xp, xlo, xhi, xplo, xphi, pairs, values, pa, sha
 
 
 # ------------------------------------------------------------------------------------------------
+# BaB level kernels (csrc/bab.hip), one launch at a time.  The native runtime launches them itself; these
+# wrappers exist so that one level can be run on hand-made state and compared with a plain oracle
+# (tests/split_cases.py).  Per-partition state and counters are updated in place, so nothing is converted
+# or copied here: a tensor of the wrong dtype, shape, device or layout raises.
+def _inplace(t, dtype, shape, name, dev=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device.type != "cuda":
+        raise ValueError(f"{name}: expected a contiguous {dtype} tensor on the GPU")
+    if dev is not None and t.device != dev:
+        raise ValueError(f"{name}: on {t.device}, the launch runs on {dev}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def _settle_kw(P, dev, pre, *, status, lvl_open, part_nodes, nodes_start, prev_start, counters_cur, counters_next,
+               host_counts, budget2, max_open, esc_budget=(), esc_open=(), part_open=None, pbudget=None, prob=None,
+               done=None):
+    """Keywords of a SettleArgs block (keys prefixed with ``pre``); the tensors are checked."""
+    i32, t = torch.int32, {}
+    t["status"] = _inplace(status, torch.int8, (P,), "status", dev)
+    for name, v in (("lvl_open", lvl_open), ("part_nodes", part_nodes), ("nodes_start", nodes_start),
+                    ("prev_start", prev_start)):
+        t[name] = _inplace(v, i32, (P,), name, dev)
+    for name, v in (("counters_cur", counters_cur), ("counters_next", counters_next), ("host_counts", host_counts)):
+        t[name] = _inplace(v, i32, (2,), name, dev)
+    if part_open is not None:
+        t["part_open"] = _inplace(part_open, i32, (P,), "part_open", dev)
+    if (pbudget is None) != (prob is None):
+        raise ValueError("pbudget and prob go together")
+    if prob is not None:
+        t["pbudget"] = _inplace(pbudget, i32, (P,), "pbudget", dev)
+        t["prob"] = _inplace(prob, torch.uint8, (P,), "prob", dev)
+    if done is not None:
+        t["done"] = _inplace(done, i32, (1,), "done", dev)
+    esc_budget, esc_open = [int(v) for v in esc_budget], [int(v) for v in esc_open]
+    if len(esc_budget) != len(esc_open) or len(esc_budget) > 4:
+        raise ValueError("esc_budget / esc_open: the same number of steps, at most 4")
+    kw = dict(_ptrs(**t), P=P, budget2=int(budget2), max_open=int(max_open), esc_budget=esc_budget,
+              esc_open=esc_open)
+    return {pre + k: v for k, v in kw.items()}
+
+
+def settle(*, status, **state):
+    """Level end in its own launch (fa_settle_kernel) on per-partition state [P], in place: ``status``
+    int8, ``lvl_open`` / ``part_nodes`` / ``nodes_start`` / ``prev_start`` int32 (``part_open``,
+    ``pbudget`` with ``prob`` uint8: optional), the level's counters ``counters_cur`` [2] int32, the
+    next slot ``counters_next`` [2] (cleared), ``budget2``, ``max_open``, ``esc_budget`` / ``esc_open``
+    (the escalation steps).  ``host_counts`` [2] int32 (device memory; allocated when left out) gets the
+    level counters and is returned."""
+    P, dev = status.shape[0], status.device
+    if P < 1:
+        raise ValueError("settle needs at least one partition")
+    if state.get("host_counts") is None:
+        state["host_counts"] = torch.zeros(2, dtype=torch.int32, device=dev)
+    if state.get("done") is not None:
+        raise ValueError("done belongs to the fused level end")
+    ext().settle(stream=_stream(dev), **_settle_kw(P, dev, "", status=status, **state))
+    return state["host_counts"]
+
+
+def split_level(*, xlo, xhi, part, open, leaf, scores, cand_x, cand_xp, pe_lb, pe_ub, olb, oub, olbp, oubp, pairs,
+                values, pa, status, part_nodes, nodes_start, prev_start, budget, budget2, m, target, cap, cand_cap,
+                xplo=None, xphi=None, ra=(), tau=0.0, shared=None, norient=None, lvl_open=None, part_open=None,
+                pbudget=None, prob=None, counters=None, pool=None, cand_buf=None, prefill=None, settle=None):
+    """One sub-batch of a BaB level (fa_split_kernel / fa_split_group_kernel) -> (pool, cand_buf, counters).
+
+    Inputs per node: boxes ``xlo`` / ``xhi`` [Nn, n0] float32 (relaxed: with ``xplo`` / ``xphi``, ``ra``,
+    ``tau`` and ``shared`` [n0] uint8), ``part`` [Nn] int32, ``open`` / ``leaf`` [Nn] uint8, ``scores``
+    [Nn, 2 n0], ``cand_x`` / ``cand_xp`` [Nn, n0], ``pe_lb`` / ``pe_ub`` [2 Nn], the row bounds ``olb``
+    ... ``oubp`` [Nn V]; ``pairs`` [Pp, 2] / ``values`` [V, npa] int64, ``pa`` the PA dims.  Per-partition
+    state [P], updated in place: ``status`` int8, ``part_nodes`` int32 (``lvl_open`` int32, ``prob``
+    uint8: optional); read: ``nodes_start``, ``prev_start`` (``pbudget``: optional).
+
+    ``pool``: dict of ``oxlo`` / ``oxhi`` (relaxed: ``oxplo`` / ``oxphi``) [cap, n0] float32 and ``opart``
+    [cap] int32; ``cand_buf`` [cand_cap, 2 n0 + 1] float32 (at least that many rows, and at least one);
+    ``counters`` [2] int32 (children, candidates).  Each is allocated when left out (the buffers filled with ``prefill``, the counters
+    zero) and returned, so a level's later sub-batches pass the first one's back in.
+
+    ``settle``: dict of the remaining :func:`settle` keywords (``counters_next``, ``host_counts``,
+    ``max_open``, ``esc_budget``, ``esc_open``, ``done`` [1] int32 zero) fuses the level end into this
+    launch; the per-partition state and ``budget2`` are this call's."""
+    f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+    if xlo.dim() != 2 or xlo.shape[0] < 1:
+        raise ValueError("xlo: expected [Nn, n0] with at least one node")
+    Nn, n0 = xlo.shape
+    dev = xlo.device
+    relaxed = xplo is not None
+    if norient is None:
+        norient = 2 if relaxed else 1
+    P = status.shape[0]
+    V, Pp = values.shape[0], pairs.shape[0]
+    pa, ra = [int(i) for i in pa], [int(i) for i in ra]
+    if any(not 0 <= i < n0 for i in pa + ra) or len(pa) > 8 or len(ra) > 8 or n0 > 64:
+        raise ValueError("PA / RA dims out of range, more than 8 of them, or n0 > 64")
+    if norient not in (1, 2) or V < 1 or cap < 0 or cand_cap < 0:
+        raise ValueError("norient, V, cap or cand_cap out of range")
+    t = dict(xlo=_inplace(xlo, f32, (Nn, n0), "xlo"), xhi=_inplace(xhi, f32, (Nn, n0), "xhi", dev),
+             part=_inplace(part, i32, (Nn,), "part", dev), open=_inplace(open, u8, (Nn,), "open", dev),
+             leaf=_inplace(leaf, u8, (Nn,), "leaf", dev), scores=_inplace(scores, f32, (Nn, 2 * n0), "scores", dev),
+             cand_x=_inplace(cand_x, f32, (Nn, n0), "cand_x", dev),
+             cand_xp=_inplace(cand_xp, f32, (Nn, n0), "cand_xp", dev),
+             pe_lb=_inplace(pe_lb, f32, (2 * Nn,), "pe_lb", dev), pe_ub=_inplace(pe_ub, f32, (2 * Nn,), "pe_ub", dev),
+             pairs=_inplace(pairs, torch.int64, (Pp, 2), "pairs", dev),
+             values=_inplace(values, torch.int64, (V, len(pa)), "values", dev),
+             status=_inplace(status, torch.int8, (P,), "status", dev),
+             part_nodes=_inplace(part_nodes, i32, (P,), "part_nodes", dev),
+             nodes_start=_inplace(nodes_start, i32, (P,), "nodes_start", dev),
+             prev_start=_inplace(prev_start, i32, (P,), "prev_start", dev))
+    for name, v in (("olb", olb), ("oub", oub), ("olbp", olbp), ("oubp", oubp)):
+        t[name] = _inplace(v, f32, (Nn * V,), name, dev)
+    if relaxed:
+        if xphi is None or shared is None:
+            raise ValueError("a relaxed level needs xplo, xphi and shared")
+        t.update(xplo=_inplace(xplo, f32, (Nn, n0), "xplo", dev), xphi=_inplace(xphi, f32, (Nn, n0), "xphi", dev),
+                 shared=_inplace(shared, u8, (n0,), "shared", dev))
+    elif xphi is not None or ra:
+        raise ValueError("xphi / ra without xplo")
+    for name, v, dt in (("lvl_open", lvl_open, i32), ("part_open", part_open, i32), ("pbudget", pbudget, i32),
+                        ("prob", prob, u8)):
+        if v is not None:
+            t[name] = _inplace(v, dt, (P,), name, dev)
+    if Nn and not 0 <= int(part.min()) <= int(part.max()) < P:
+        raise ValueError("part indexes the per-partition state [P]")
+    if Pp and not 0 <= int(pairs.min()) <= int(pairs.max()) < V:
+        raise ValueError("pairs index values [V, npa]")
+
+    def new(*shape, dtype=f32):
+        o = torch.empty(*shape, dtype=dtype, device=dev)
+        return o if prefill is None else o.fill_(prefill)
+
+    rows, crows = max(cap, 1), max(cand_cap, 1)     # a capacity of 0 still gets a buffer: no null pointers
+    if pool is None:
+        pool = dict(oxlo=new(rows, n0), oxhi=new(rows, n0), opart=new(rows, dtype=i32))
+        if relaxed:
+            pool.update(oxplo=new(rows, n0), oxphi=new(rows, n0))
+    for name in ("oxlo", "oxhi") + (("oxplo", "oxphi") if relaxed else ()):
+        t[name] = _inplace(pool[name], f32, None, name, dev)
+    t["opart"] = _inplace(pool["opart"], i32, None, "opart", dev)
+    if cand_buf is None:
+        cand_buf = new(crows, 2 * n0 + 1)
+    t["cand_buf"] = _inplace(cand_buf, f32, None, "cand_buf", dev)
+    # buffers may be longer than the capacity (guard rows that must stay untouched), never shorter
+    for name, v in t.items():
+        if name in ("oxlo", "oxhi", "oxplo", "oxphi") and (v.dim() != 2 or v.shape[1] != n0 or v.shape[0] < rows):
+            raise ValueError(f"{name}: expected [>= {rows}, {n0}], got {tuple(v.shape)}")
+    if t["opart"].dim() != 1 or t["opart"].shape[0] < rows:
+        raise ValueError(f"opart: expected at least {rows} entries")
+    if cand_buf.dim() != 2 or cand_buf.shape[1] != 2 * n0 + 1 or cand_buf.shape[0] < crows:
+        raise ValueError(f"cand_buf: expected [>= {crows}, {2 * n0 + 1}], got {tuple(cand_buf.shape)}")
+    if counters is None:
+        counters = torch.zeros(2, dtype=i32, device=dev)
+    _inplace(counters, i32, (2,), "counters", dev)
+    extra = {}
+    if settle is not None:
+        extra = _settle_kw(P, dev, "settle_", status=status, lvl_open=lvl_open, part_nodes=part_nodes,
+                           nodes_start=nodes_start, prev_start=prev_start, counters_cur=counters,
+                           part_open=part_open, pbudget=pbudget, prob=prob, budget2=budget2, **settle)
+        if "settle_done" not in extra:
+            raise ValueError("the fused level end needs done")
+    ext().split_level(Nn=Nn, n0=n0, relaxed=int(relaxed), V=V, Pp=Pp, norient=norient, ra=ra, tau=float(tau), pa=pa,
+                      budget=int(budget), budget2=int(budget2), m=int(m), target=int(target), cap=int(cap),
+                      cand_cap=int(cand_cap), count_out=counters.data_ptr(), cand_count=counters[1:].data_ptr(),
+                      stream=_stream(dev), **_ptrs(**t), **extra)
+    return pool, cand_buf, counters
+
+
+def bab_init(status0, run, lo, hi, *, budget, ra=(), tau=0.0, relaxed=False, escalate=False):
+    """Solve start (fa_bab_init_kernel) from the staged block of ``status0`` [P] int8 (host), the running
+    partition ids ``run`` [n_run] and their boxes ``lo`` / ``hi`` [n_run, n0] -> dict of the device state:
+    ``status``, ``nodes``, ``open_left``, ``lvl_open``, ``nodes_start``, ``prev_start`` [P], the root pool
+    ``part``, ``xlo``, ``xhi`` (relaxed: ``xplo``, ``xphi``), ``counters`` [5] and, with ``escalate``,
+    ``pbudget`` / ``prob``.  Everything starts filled with a sentinel (-7 / 0xF9) the kernel must
+    overwrite."""
+    import numpy as np
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    st = np.ascontiguousarray(status0, np.int8)
+    run = np.ascontiguousarray(run, np.int32)
+    lo, hi = np.ascontiguousarray(lo, np.float32), np.ascontiguousarray(hi, np.float32)
+    P, n_run = st.shape[0], run.shape[0]
+    if lo.ndim != 2 or lo.shape != hi.shape or lo.shape[0] != n_run or P < 1 or n_run < 1:
+        raise ValueError("lo / hi: expected [n_run, n0], with at least one partition running")
+    n0 = lo.shape[1]
+    ra = [int(i) for i in ra]
+    if any(not 0 <= i < n0 for i in ra) or len(ra) > 8:
+        raise ValueError("RA dims out of range")
+    if n_run and not 0 <= int(run.min()) <= int(run.max()) < P:
+        raise ValueError("run indexes the partitions")
+    block = st.tobytes() + b"\0" * (-P % 4) + run.tobytes() + lo.tobytes() + hi.tobytes()
+    stage = torch.frombuffer(bytearray(block), dtype=torch.uint8).to(dev)
+
+    def new(*shape, dtype=torch.int32):
+        return torch.full(shape, -7, dtype=dtype, device=dev)
+
+    s = dict(status=new(P, dtype=torch.int8), nodes=new(P), open_left=new(P), lvl_open=new(P), nodes_start=new(P),
+             prev_start=new(P), part=new(n_run), xlo=new(n_run, n0, dtype=torch.float32),
+             xhi=new(n_run, n0, dtype=torch.float32), counters=new(5))
+    if relaxed:
+        s.update(xplo=new(n_run, n0, dtype=torch.float32), xphi=new(n_run, n0, dtype=torch.float32))
+    if escalate:
+        s.update(pbudget=new(P), prob=torch.full((P,), 0xF9, dtype=torch.uint8, device=dev))
+    ext().bab_init(P=P, n_run=n_run, n0=n0, ra=ra if relaxed else [], tau=float(tau), budget=int(budget),
+                   stream=_stream(dev), stage=stage.data_ptr(), **_ptrs(**s))
+    torch.cuda.current_stream(dev).synchronize()      # the staged block lives until the kernel has read it
+    return s
+
+
+def bab_finish(status, nodes, open_left):
+    """Solve end (fa_bab_finish_kernel): [3, P] int32 = status, nodes, open_left."""
+    P, dev = status.shape[0], status.device
+    _inplace(status, torch.int8, (P,), "status")
+    _inplace(nodes, torch.int32, (P,), "nodes", dev)
+    _inplace(open_left, torch.int32, (P,), "open_left", dev)
+    out = torch.full((3, P), -7, dtype=torch.int32, device=dev)
+    if P:
+        ext().bab_finish(P=P, stream=_stream(dev), **_ptrs(status=status, nodes=nodes, open_left=open_left, out=out))
+    return out
+
+
+def mark_unknown(part, status):
+    """Time budget hit (fa_mark_unknown_kernel): the RUNNING / STOPPING partitions among ``part`` [n]
+    int32 become UNKNOWN in ``status`` [P] int8, in place."""
+    n, P, dev = part.shape[0], status.shape[0], status.device
+    _inplace(status, torch.int8, (P,), "status")
+    _inplace(part, torch.int32, (n,), "part", dev)
+    if n and not 0 <= int(part.min()) <= int(part.max()) < P:
+        raise ValueError("part indexes status [P]")
+    if n:
+        ext().mark_unknown(n=n, stream=_stream(dev), **_ptrs(part=part, status=status))
+
+
+def set_status(idx, status, v: int):
+    """``status[idx] = v`` (fa_set_status_kernel), in place; ``idx`` [n] int32."""
+    n, P, dev = idx.shape[0], status.shape[0], status.device
+    _inplace(status, torch.int8, (P,), "status")
+    _inplace(idx, torch.int32, (n,), "idx", dev)
+    if n and not 0 <= int(idx.min()) <= int(idx.max()) < P:
+        raise ValueError("idx indexes status [P]")
+    if not -128 <= int(v) <= 127:
+        raise ValueError("v: an int8 status")
+    if n:
+        ext().set_status(n=n, v=int(v), stream=_stream(dev), **_ptrs(idx=idx, status=status))
+
+
+# ------------------------------------------------------------------------------------------------
 def _parse_sim_blocks(v: Optional[str]) -> int:
     if v is None or v.strip() == "":
         return 0
