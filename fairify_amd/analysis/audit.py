@@ -26,8 +26,10 @@ import numpy as np
 
 from .. import presets
 from ..engine.audit import AuditResult, audit_rows, lowest_bit, witness, witnesses
+from ..engine.neighbours import audit_neighbours, exposure
 from ..models.zoo import get_model
 from ..ops import audit as A
+from ..ops import neighbours as NB
 from ..ops.backend import Backend
 from .hybrid import NOT_ATTEMPTED, V_SAT, V_UNKNOWN, V_UNSAT, VerdictTable
 from .rate import SoundnessError
@@ -115,12 +117,19 @@ def _fmt_values(values: np.ndarray, mask: int) -> str:
 def audit_preset(preset: str, model: str, data: Optional[str] = None, split: str = "all",
                  results: Optional[str] = None, weights: str = "zoo", seed: int = 0, device: str = "cpu",
                  max_rows: Optional[int] = None, out_dir: Optional[str] = None,
-                 pairs_out: Optional[str] = None) -> Dict:
+                 pairs_out: Optional[str] = None, neighbours: bool = False, radius=None,
+                 radius_of: Optional[Dict] = None) -> Dict:
     """Audit ``model`` on the rows of ``data`` (or of the preset's dataset) under the query of
     ``preset``; ``results``: the directory of a verify run (``<model>.csv``) for the verdict
     cross-check.  Writes ``audit.csv`` / ``audit.json`` to ``out_dir`` and, with ``pairs_out``, an
     ``.npz`` of one exactly confirmed pair (``x``, ``xp``) per flagged row, which
-    ``repair --counterexamples`` reads.  Returns the summary."""
+    ``repair --counterexamples`` reads.  Returns the summary.
+
+    ``neighbours``: also decide every single-attribute neighbour of every row
+    (``engine/neighbours.py``; ``radius``: an integer or ``'full'`` for every non-protected
+    feature, ``radius_of``: per feature name) and write ``neighbours.csv`` / ``neighbours.json``;
+    the summary then carries a ``"neighbours"`` entry, and ``audit.csv`` / ``audit.json`` are the
+    bytes they are without it."""
     pre = presets.get(preset)
     grid = pre.grid(seed=seed)
     q = pre.resolved()
@@ -161,5 +170,73 @@ def audit_preset(preset: str, model: str, data: Optional[str] = None, split: str
                             [int(res.own[i] >= 0), int(inside[i]), int(ids[i]), _NAMES[int(verdict[i])], int(m != 0),
                              int(res.direction[i]), m, _fmt_values(values, m)])
         with open(os.path.join(out_dir, "audit.json"), "w") as fp:
+            json.dump(out, fp, indent=2)
+    if neighbours:
+        out = dict(out)
+        out["neighbours"] = _neighbours(be, grid, table, q, mlp, X, res, values, radius, radius_of, out_dir)
+    return out
+
+
+def neighbour_cross_check(be, grid, table: Optional[VerdictTable], q, mlp, X: np.ndarray, nres, values) -> int:
+    """The flagged neighbours that lie in UNSAT partitions, deduplicated, audited as rows of their own
+    and passed through :func:`cross_check` (which raises :class:`SoundnessError` on a
+    contradiction).  Returns how many were checked."""
+    if table is None:
+        return 0
+    rows, js = np.nonzero(NB.unpack_bits(nres.flag, nres.table.M))
+    if not rows.size:
+        return 0
+    t = nres.table
+    Z = X[rows].copy()
+    d = t.dim[js].astype(np.int64)
+    at = np.arange(len(rows))
+    Z[at, d] = np.where(t.abs[js] != 0, t.off[js].astype(np.int64), Z[at, d] + t.off[js])
+    ids = grid.encode(Z)
+    keep = ids >= 0
+    keep[keep] = table.table[ids[keep]] == V_UNSAT
+    Z = np.unique(Z[keep], axis=0)
+    if len(Z):
+        cross_check(grid, table, q, mlp, Z, audit_rows(be, q, Z), values)
+    return int(len(Z))
+
+
+def _neighbours(be, grid, table, q, mlp, X, res: AuditResult, values, radius, radius_of, out_dir) -> Dict:
+    """The ``--neighbours`` part of :func:`audit_preset`: summary dictionary, and the two files."""
+    dom = q.domain
+    radii = {"*": radius}
+    radii.update(radius_of or {})
+    nres = audit_neighbours(be, q, X, radii=radii)
+    ex = exposure(nres, X, res.flip_mask != 0)
+    t = nres.table
+    feats = [k for k in range(q.n) if k not in q.pa_idx]
+    n_valid = 0                                                     # valid neighbours of audited rows, in chunks
+    for s0 in range(0, len(X), 4096):
+        sl = slice(s0, s0 + 4096)
+        n_valid += int(NB.neighbour_values(X[sl], t)[1][nres.own[sl] >= 0].sum())
+    checked = neighbour_cross_check(be, grid, table, q, mlp, X, nres, values)
+    audited = nres.own >= 0
+    cls = np.where(ex.flagged, "flagged", np.where(ex.exposed, "exposed", np.where(ex.robust, "robust", "")))
+    out = {"radii": {dom.names[k]: ("full" if t.radius[k] >= NB.FULL else int(t.radius[k])) for k in feats},
+           "M": t.M, "audited": int(audited.sum()), "flagged": int(ex.flagged.sum()),
+           "exposed": int(ex.exposed.sum()), "robust": int(ex.robust.sum()),
+           "valid_neighbours": n_valid, "flagged_neighbours": int(ex.count.sum()),
+           "features": {dom.names[k]: {"rows_exposed": int((ex.exposed & (ex.count[:, k] > 0)).sum()),
+                                       "flagged_neighbours": int(ex.count[:, k].sum())} for k in feats},
+           "ambiguous_left": int(nres.ambiguous_left), "checked_against_results": table is not None,
+           "neighbours_in_unsat_checked": checked}
+    if out_dir:
+        total = ex.count.sum(axis=1)
+        with open(os.path.join(out_dir, "neighbours.csv"), "w", newline="") as fp:
+            wr = csv.writer(fp)
+            head = ["row", "audited", "flagged", "class", "flagged_neighbours"]
+            for k in feats:
+                head += [dom.names[k] + "_count", dom.names[k] + "_nearest"]
+            wr.writerow(head)
+            for i in range(len(X)):
+                line = [i, int(audited[i]), int(ex.flagged[i]), cls[i], int(total[i])]
+                for k in feats:
+                    line += [int(ex.count[i, k]), int(ex.nearest[i, k])]
+                wr.writerow(line)
+        with open(os.path.join(out_dir, "neighbours.json"), "w") as fp:
             json.dump(out, fp, indent=2)
     return out

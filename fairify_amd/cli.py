@@ -8,6 +8,7 @@
     python -m fairify_amd.cli measure --preset src/GC-age --model GC-1 --results results/gc --out results/gc-rate
     python -m fairify_amd.cli measure --preset src/GC-age --model GC-1 --certify [--node-budget N] [--leaf-points K]
     python -m fairify_amd.cli audit --preset src/AC-sex --model AC-3 [--data rows.csv] [--results results/ac] --out ...
+    python -m fairify_amd.cli audit --preset src/GC-age --model GC-1 --neighbours --radius-of credit_amount=3 --out ...
     python -m fairify_amd.cli repair --model AC-3 --counterexamples results/ac3/counterexamples.csv ...
     python -m fairify_amd.cli export-cex --preset src/AC-sex --model AC-3 --results results/ac
 
@@ -118,8 +119,20 @@ def cmd_audit(args):
 
     out = audit_preset(args.preset, args.model, data=args.data, split=args.split, results=args.results,
                        weights=args.weights, seed=args.seed, device=_device(args.device), max_rows=args.max_rows,
-                       out_dir=args.out, pairs_out=args.pairs_out)
+                       out_dir=args.out, pairs_out=args.pairs_out, neighbours=args.neighbours, radius=args.radius,
+                       radius_of=_radius_of(args.radius_of))
     print(json.dumps(out, indent=2, default=float))
+
+
+def _radius_of(items):
+    """``name=R`` arguments -> {name: R}."""
+    out = {}
+    for it in items or []:
+        name, sep, r = it.partition("=")
+        if not sep or not name or not r:
+            raise SystemExit(f"--radius-of {it!r}: expected name=R with R an integer or 'full'")
+        out[name] = r
+    return out
 
 
 def cmd_repair(args):
@@ -301,6 +314,14 @@ def main(argv=None):
     au.add_argument("--seed", type=int, default=0)
     au.add_argument("--weights", default="zoo")
     au.add_argument("--device", default=None)
+    au.add_argument("--neighbours", action="store_true",
+                    help="also decide every row's single-attribute neighbours (one non-protected attribute set to "
+                         "another value of its domain): neighbours.csv / neighbours.json with the rows that are "
+                         "flagged, exposed (a flagged neighbour) or robust (a proof that there is none)")
+    au.add_argument("--radius", default="full",
+                    help="--neighbours: largest change of an attribute, an integer or 'full' (the whole range)")
+    au.add_argument("--radius-of", action="append", default=[], metavar="NAME=R",
+                    help="--neighbours: radius of one feature (repeatable); wide features need one")
     au.add_argument("--out", default=None, help="directory for audit.csv / audit.json")
     au.set_defaults(fn=cmd_audit)
 

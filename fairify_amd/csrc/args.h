@@ -629,3 +629,34 @@ struct AuditArgs {
   int8_t* own_sign;         // [N] -1: u < 0, +1: l > 0, else 0
   int blocks;               // workgroups (64-row passes strided over them)
 };
+
+// Single-attribute neighbourhood of real individuals (csrc/neighbours.hip, definitions in
+// ops/neighbours.py): AuditArgs' inputs plus the neighbour table; bit j % 32 of word j / 32 of a row's
+// cert / poss words is neighbour j.  No atomics.
+struct NeighbourArgs {
+  const float* flat;
+  const float* x;           // [N, n0] integral rows
+  const int* own;           // [N] index of the row's PA coordinates in values, -1: outside the PA domain
+  int N;
+  int V;
+  int npa;
+  int pa_idx[FA_MAX_PA];
+  const int64_t* values;    // [V, npa]
+  int Pp;
+  const int64_t* pairs;     // [Pp, 2]
+  int nra;
+  int ra_idx[FA_MAX_RA];
+  int tau;
+  int E;
+  int M;                    // neighbour table entries
+  int W;                    // ceil(M / 32) words per row
+  const int* nb_dim;        // [M] the overwritten (non-PA) coordinate
+  const int* nb_off;        // [M] its new value (abs) or the offset from the row's own (relative)
+  const int* nb_abs;        // [M] 1: absolute entry
+  const int* dom_lo;        // [n0] domain range
+  const int* dom_hi;
+  const int* radius;        // [n0] largest |c - x_k|; INT_MAX: full
+  int* cert;                // [N, W]
+  int* poss;                // [N, W]
+  int blocks;               // workgroups ((64-row pass, word) items strided over them)
+};

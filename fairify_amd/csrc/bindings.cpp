@@ -37,6 +37,7 @@ extern "C" int fa_crown_shaped(const NetDesc& net, int mask);
 extern "C" int fa_refine_shaped(const NetDesc& net, int logit);
 extern "C" int fa_rate_launch(const NetDesc& net, RateArgs a, hipStream_t stream);
 extern "C" int fa_audit_launch(const NetDesc& net, AuditArgs a, hipStream_t stream);
+extern "C" int fa_neighbour_launch(const NetDesc& net, NeighbourArgs a, hipStream_t stream);
 extern "C" int fa_count_enum_launch(const NetDesc& net, EnumArgs a, hipStream_t stream);
 extern "C" int fa_count_rows_launch(CountArgs a, hipStream_t stream);
 extern "C" int fa_count_level_launch(CountArgs a, hipStream_t stream);
@@ -521,6 +522,50 @@ PYBIND11_MODULE(_C, m) {
     if (rc == -3) return false;
     if (rc == -2) throw std::invalid_argument("audit: workgroup count outside 1..number of 64-row passes");
     ckl(rc, "audit");
+    return true;
+  });
+
+  // single-attribute neighbourhood of real rows (csrc/neighbours.hip): cert / poss words [N, W].  Returns
+  // false when the kernel does not cover the shape (the caller takes the composed path)
+  m.def("neighbours", [](const Net& net, py::kwargs kw) {
+    Kw k("neighbours", kw);
+    NeighbourArgs a{};
+    a.flat = k.need<const float>("flat");
+    a.x = k.need<const float>("x");
+    a.own = k.need<const int>("own");
+    a.N = k.i("N");
+    a.V = k.i("V");
+    a.npa = dims(k, "pa", a.pa_idx, FA_MAX_PA, "too many PA/RA dims");
+    a.values = k.need<const int64_t>("values");
+    a.Pp = k.i("Pp");
+    a.pairs = k.ptr<const int64_t>("pairs");
+    a.nra = dims(k, "ra", a.ra_idx, FA_MAX_RA, "too many PA/RA dims");
+    a.tau = k.i("tau");
+    a.E = k.i("E");
+    a.M = k.i("M");
+    a.W = k.i("W");
+    a.nb_dim = k.need<const int>("nb_dim");
+    a.nb_off = k.need<const int>("nb_off");
+    a.nb_abs = k.need<const int>("nb_abs");
+    a.dom_lo = k.need<const int>("dom_lo");
+    a.dom_hi = k.need<const int>("dom_hi");
+    a.radius = k.need<const int>("radius");
+    a.cert = k.need<int>("cert");
+    a.poss = k.need<int>("poss");
+    a.blocks = k.i("blocks");
+    if (a.N < 0 || a.M < 0) throw std::invalid_argument("neighbours: negative row or neighbour count");
+    if (a.W != (a.M + 31) / 32) throw std::invalid_argument("neighbours: W is not ceil(M / 32)");
+    if (a.Pp > 0 && !a.pairs) throw py::type_error("neighbours() missing required keyword argument 'pairs'");
+    for (int q = 0; q < a.npa; ++q)
+      if (a.pa_idx[q] < 0 || a.pa_idx[q] >= net.d.dims[0])
+        throw std::invalid_argument("neighbours: PA dim outside the inputs");
+    for (int q = 0; q < a.nra; ++q)
+      if (a.ra_idx[q] < 0 || a.ra_idx[q] >= net.d.dims[0])
+        throw std::invalid_argument("neighbours: RA dim outside the inputs");
+    const int rc = fa_neighbour_launch(net.d, a, finish(k));
+    if (rc == -3) return false;
+    if (rc == -2) throw std::invalid_argument("neighbours: workgroup count outside 1..passes x words");
+    ckl(rc, "neighbours");
     return true;
   });
 

@@ -10,6 +10,7 @@ import os
 import threading
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import ext
@@ -937,6 +938,85 @@ def audit_masks(be, q, X, own, values, pairs, blocks: Optional[int] = None):
         if not ok:
             return None
     return cert, poss, sign
+
+
+def neighbours_fused() -> bool:
+    """``FAIRIFY_NEIGHBOURS_FUSED=0`` (read per call) sends ``engine/neighbours.py`` down the composed
+    path -- the audit kernel fed materialised neighbours -- for A/B runs; anything else the fused kernel."""
+    return os.environ.get("FAIRIFY_NEIGHBOURS_FUSED", "1").strip() != "0"
+
+
+def neighbour_items(N: int, M: int) -> int:
+    """(64-row pass, word) work items of ``fa_neighbour_kernel``: the largest workgroup count."""
+    return audit_passes(N) * max(1, (int(M) + 31) // 32)
+
+
+def neighbour_masks(be, q, X, own, values, pairs, table, radii=None, blocks: Optional[int] = None):
+    """Per-(row, neighbour) bits of rows ``X`` [N, n0] in one fused launch (``fa_neighbour_kernel``,
+    definitions in ops/neighbours.py): (cert, poss) int32 [N, W], or ``None`` when the kernel does not
+    cover the shape (the audit kernel's conditions): the caller takes
+    ``ops/neighbours.neighbour_masks_ref``.  ``table``: an ``ops/neighbours.NeighbourTable``;
+    ``radii``: [n0] per-feature radii (default: the table's).  ``blocks``: workgroups (default: one
+    per work item, at most 1 024); every value gives the same outputs."""
+    from .audit import MAX_VALUES
+    from .neighbours import FULL, MAX_NEIGHBOURS
+    from .rate import MAX_OFFSETS, offset_vectors
+
+    if X.dim() != 2 or X.shape[1] != be.n0:
+        raise ValueError(f"X: expected [N, {be.n0}], got {tuple(X.shape)}")
+    N = int(X.shape[0])
+    dev = X.device
+    npa = len(q.pa_idx)
+    if values.dim() != 2 or values.shape[1] != npa:
+        raise ValueError(f"values: expected [V, {npa}], got {tuple(values.shape)}")
+    V, Pp = int(values.shape[0]), int(pairs.shape[0])
+    if not 1 <= V <= MAX_VALUES:
+        raise ValueError(f"neighbours: {V} PA assignments, the kernel covers 1..{MAX_VALUES}")
+    X = _c(X, torch.float32, (N, be.n0), "X")
+    own = _c(own, torch.int32, (N,), "own")
+    values = _c(values, torch.int64, (V, npa), "values")
+    pairs = _c(pairs, torch.int64, (Pp, 2), "pairs")
+    if any(t.device != dev for t in (own, values, pairs, be.flat)):
+        raise ValueError("neighbours: X, own, values, pairs and the network must be on one device")
+    if Pp and (int(pairs.min()) < 0 or int(pairs.max()) >= V):
+        raise ValueError("pairs: index outside [0, V)")
+    if N:
+        omin, omax = torch.stack(torch.aminmax(own)).tolist()           # one read-back
+        if omin < -1 or omax >= V:
+            raise ValueError("own: index outside [-1, V)")
+    E = int(offset_vectors(q).shape[0])                    # raises over MAX_OFFSETS
+    assert E <= MAX_OFFSETS
+    M, W = table.M, table.W
+    if M > MAX_NEIGHBOURS:
+        raise ValueError(f"neighbours: {M} table entries, at most {MAX_NEIGHBOURS}")
+    radii = table.radius if radii is None else np.asarray(radii, dtype=np.int64)
+    if radii.shape != (be.n0,) or table.lo.shape != (be.n0,) or table.hi.shape != (be.n0,):
+        raise ValueError(f"neighbours: radii and the domain range must have {be.n0} entries")
+    if radii.min(initial=0) < 0 or radii.max(initial=0) > FULL:
+        raise ValueError(f"neighbours: radius outside 0..{FULL}")
+    if M and (int(table.dim.min()) < 0 or int(table.dim.max()) >= be.n0 or set(table.dim.tolist()) & set(q.pa_idx)):
+        raise ValueError("neighbours: table dimension outside the non-PA inputs")
+    if blocks is None:
+        blocks = min(neighbour_items(N, M), _AUDIT_BLOCKS)
+    if not 1 <= int(blocks) <= neighbour_items(N, M):
+        raise ValueError(f"neighbours: {blocks} workgroups outside 1..{neighbour_items(N, M)}")
+    cert = torch.zeros(N, W, dtype=torch.int32, device=dev)
+    poss = torch.zeros(N, W, dtype=torch.int32, device=dev)
+    if max([be.n0] + list(be.widths)) > 160 or be.n0 > 32:
+        return None
+    if N and M:
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64).clip(-FULL - 1, FULL)
+                                         .astype(np.int32)).to(dev)
+        tabs = dict(nb_dim=i32(table.dim), nb_off=i32(table.off), nb_abs=i32(table.abs), dom_lo=i32(table.lo),
+                    dom_hi=i32(table.hi), radius=i32(radii))
+        ok = ext().neighbours(_net(be), **_ptrs(flat=be.flat, x=X, own=own, values=values,
+                                                pairs=pairs if Pp else None, cert=cert, poss=poss, **tabs),
+                              N=N, V=V, pa=list(q.pa_idx), Pp=Pp, ra=list(q.ra_idx) if q.relaxed else [],
+                              tau=int(q.tau) if q.relaxed else 0, E=E, M=M, W=W, blocks=int(blocks),
+                              stream=_stream(dev))
+        if not ok:
+            return None
+    return cert, poss
 
 
 # Workgroups of a leaf list: at least 1 024 (4 per CU), and enough that a workgroup enumerates about
