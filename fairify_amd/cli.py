@@ -9,6 +9,7 @@
     python -m fairify_amd.cli measure --preset src/GC-age --model GC-1 --certify [--node-budget N] [--leaf-points K]
     python -m fairify_amd.cli audit --preset src/AC-sex --model AC-3 [--data rows.csv] [--results results/ac] --out ...
     python -m fairify_amd.cli audit --preset src/GC-age --model GC-1 --neighbours --radius-of credit_amount=3 --out ...
+    python -m fairify_amd.cli causal --preset src/AC-sex --model AC-3 --max-values 10 --out results/ac3-causal
     python -m fairify_amd.cli repair --model AC-3 --counterexamples results/ac3/counterexamples.csv ...
     python -m fairify_amd.cli export-cex --preset src/AC-sex --model AC-3 --results results/ac
 
@@ -121,6 +122,17 @@ def cmd_audit(args):
                        weights=args.weights, seed=args.seed, device=_device(args.device), max_rows=args.max_rows,
                        out_dir=args.out, pairs_out=args.pairs_out, neighbours=args.neighbours, radius=args.radius,
                        radius_of=_radius_of(args.radius_of))
+    print(json.dumps(out, indent=2, default=float))
+
+
+def cmd_causal(args):
+    from .analysis.causal_sets import causal_preset
+
+    out = causal_preset(args.preset, args.model, max_size=args.max_size, samples=args.samples, seed=args.seed,
+                        threshold=args.threshold, conf=args.conf, margin=args.margin, min_samples=args.min_samples,
+                        values=args.values, max_values=args.max_values, max_assignments=args.max_assignments,
+                        base=args.base, data=args.data, split=args.split, weights=args.weights,
+                        device=_device(args.device), out_dir=args.out, pairs_out=args.pairs_out)
     print(json.dumps(out, indent=2, default=float))
 
 
@@ -324,6 +336,44 @@ def main(argv=None):
                     help="--neighbours: radius of one feature (repeatable); wide features need one")
     au.add_argument("--out", default=None, help="directory for audit.csv / audit.json")
     au.set_defaults(fn=cmd_audit)
+
+    ca = sub.add_parser("causal", help="search attribute sets (1..4 attributes) for causal discrimination: which "
+                                       "attributes do the decisions depend on at all",
+                        description="Themis's discrimination search with exact flip bits.  One base table is shared "
+                                    "by all sets (the reference draws one per set).  A set has at most 4 attributes "
+                                    "and at most --max-assignments assignments; the fused GPU kernel covers networks "
+                                    "with at most 32 inputs, layers up to 160 wide and 64 KB of staged weights and "
+                                    "is the default there (FAIRIFY_CAUSAL_FUSED=0: the composed path); other shapes "
+                                    "take the composed path.  Writes causal.csv / causal.json.")
+    ca.add_argument("--preset", required=True)
+    ca.add_argument("--model", required=True)
+    ca.add_argument("--max-size", type=int, default=2, choices=[1, 2, 3, 4], help="largest attribute set")
+    ca.add_argument("--samples", type=int, default=1000,
+                    help="base rows; one table is shared by all sets (common random numbers)")
+    ca.add_argument("--seed", type=int, default=42, help="seed of the drawn base table")
+    ca.add_argument("--threshold", type=float, default=0.15, help="a set is discriminatory above this rate")
+    ca.add_argument("--conf", type=float, default=0.99)
+    ca.add_argument("--margin", type=float, default=0.01)
+    ca.add_argument("--min-samples", type=int, default=100)
+    ca.add_argument("--values", default="data", choices=["data", "domain"],
+                    help="value lists: the values observed in the dataset (default), or the whole range lo..hi")
+    ca.add_argument("--max-values", type=int, default=None, metavar="K",
+                    help="thin a longer list to K values evenly spaced by rank, first and last kept")
+    ca.add_argument("--max-assignments", type=int, default=4096,
+                    help="a set with more assignments (the product of its list sizes) is not tested")
+    ca.add_argument("--base", default="sampled", choices=["sampled", "data"],
+                    help="base rows: drawn from the value lists, or the first --samples real rows (0: all)")
+    ca.add_argument("--data", default=None,
+                    help="CSV of encoded integer rows whose header holds the domain's feature names "
+                         "(default: the suite's dataset)")
+    ca.add_argument("--split", default="all", choices=["all", "train", "test"], help="without --data: which rows")
+    ca.add_argument("--pairs-out", default=None,
+                    help="FILE.npz: the exactly confirmed pair (x, xp) of every discriminatory set, for "
+                         "repair --counterexamples")
+    ca.add_argument("--weights", default="zoo")
+    ca.add_argument("--device", default=None)
+    ca.add_argument("--out", default=None, help="directory for causal.csv / causal.json")
+    ca.set_defaults(fn=cmd_causal)
 
     r = sub.add_parser("repair", help="bias localisation + masked fine-tune / counterexample retraining")
     r.add_argument("--model", required=True)

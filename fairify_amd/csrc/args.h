@@ -660,3 +660,23 @@ struct NeighbourArgs {
   int* poss;                // [N, W]
   int blocks;               // workgroups ((64-row pass, word) items strided over them)
 };
+
+// Causal-discrimination search over attribute sets (csrc/causal.hip, definitions in ops/causal.py): the
+// attribute set plays the part of the protected attributes; its assignments (the mixed-radix product of
+// its features' value lists, last feature fastest) are walked with an odometer and never materialised.
+// One byte per (row, set): bit 0 poss, bit 1 cert.  No atomics.
+struct CausalArgs {
+  const float* flat;
+  const float* x;           // [S, n0] integral base rows
+  int S;
+  int T;                    // attribute sets of this launch
+  int D;                    // columns of dims (the kernel covers exactly 4)
+  const int* dims;          // [T, D] strictly increasing feature indices, padded with -1
+  const int* vals;          // [nvals] every feature's value list, flat
+  const int* voff;          // [n0 + 1] feature k's list is vals[voff[k] .. voff[k + 1])
+  int nvals;
+  const int* h_dims;        // host copies of dims and voff: the launcher's checks
+  const int* h_voff;
+  uint8_t* code;            // [S, T]
+  int blocks;               // workgroups ((64-row pass, set) items strided over them)
+};

@@ -38,6 +38,7 @@ extern "C" int fa_refine_shaped(const NetDesc& net, int logit);
 extern "C" int fa_rate_launch(const NetDesc& net, RateArgs a, hipStream_t stream);
 extern "C" int fa_audit_launch(const NetDesc& net, AuditArgs a, hipStream_t stream);
 extern "C" int fa_neighbour_launch(const NetDesc& net, NeighbourArgs a, hipStream_t stream);
+extern "C" int fa_causal_launch(const NetDesc& net, CausalArgs a, hipStream_t stream);
 extern "C" int fa_count_enum_launch(const NetDesc& net, EnumArgs a, hipStream_t stream);
 extern "C" int fa_count_rows_launch(CountArgs a, hipStream_t stream);
 extern "C" int fa_count_level_launch(CountArgs a, hipStream_t stream);
@@ -566,6 +567,44 @@ PYBIND11_MODULE(_C, m) {
     if (rc == -3) return false;
     if (rc == -2) throw std::invalid_argument("neighbours: workgroup count outside 1..passes x words");
     ckl(rc, "neighbours");
+    return true;
+  });
+
+  // causal-discrimination search over attribute sets (csrc/causal.hip): one byte per (row, set), bit 0
+  // poss, bit 1 cert.  set_dims / value_off: the host copies of dims [T, D] and voff [n0 + 1], which the
+  // checks here and in the launcher read.  Returns false when the kernel does not cover the shape (the
+  // caller takes the composed path)
+  m.def("causal", [](const Net& net, py::kwargs kw) {
+    Kw k("causal", kw);
+    CausalArgs a{};
+    a.flat = k.need<const float>("flat");
+    a.x = k.need<const float>("x");
+    a.S = k.i("S");
+    a.T = k.i("T");
+    a.D = k.i("D");
+    a.dims = k.need<const int>("dims");
+    a.vals = k.need<const int>("vals");
+    a.voff = k.need<const int>("voff");
+    a.nvals = k.i("nvals");
+    const std::vector<int> set_dims = k.ints("set_dims");
+    const std::vector<int> value_off = k.ints("value_off");
+    a.h_dims = set_dims.data();
+    a.h_voff = value_off.data();
+    a.code = k.need<uint8_t>("code");
+    a.blocks = k.i("blocks");
+    if (a.S < 0 || a.T < 0) throw std::invalid_argument("causal: negative row or set count");
+    if (a.D < 1) throw std::invalid_argument("causal: a set needs at least one dim");
+    if (set_dims.size() != (size_t)a.T * (size_t)a.D) throw std::invalid_argument("causal: set_dims is not [T, D]");
+    if (value_off.size() != (size_t)net.d.dims[0] + 1)
+      throw std::invalid_argument("causal: value_off is not one offset per input plus the end");
+    if (value_off.front() != 0 || value_off.back() != a.nvals)
+      throw std::invalid_argument("causal: value_off does not span vals");
+    for (size_t i = 1; i < value_off.size(); ++i)
+      if (value_off[i] <= value_off[i - 1]) throw std::invalid_argument("causal: a feature without values");
+    const int rc = fa_causal_launch(net.d, a, finish(k));
+    if (rc == -3) return false;
+    if (rc == -2) throw std::invalid_argument("causal: workgroup count outside 1..passes x sets");
+    ckl(rc, "causal");
     return true;
   });
 

@@ -1019,6 +1019,71 @@ def neighbour_masks(be, q, X, own, values, pairs, table, radii=None, blocks: Opt
     return cert, poss
 
 
+def causal_fused() -> bool:
+    """``FAIRIFY_CAUSAL_FUSED=0`` (read per call) sends ``engine/causal.py`` down the composed path --
+    ``point_bounds`` fed materialised altered rows -- for A/B runs; anything else the fused kernel,
+    the default on the shapes it covers (profiles/r20/causal/README.md)."""
+    return os.environ.get("FAIRIFY_CAUSAL_FUSED", "1").strip() != "0"
+
+
+def causal_items(S: int, T: int) -> int:
+    """(64-row pass, attribute set) work items of ``fa_causal_kernel``: the largest workgroup count."""
+    return audit_passes(S) * max(1, int(T))
+
+
+def causal_codes(be, X, table, blocks: Optional[int] = None):
+    """Per-(base row, attribute set) bytes of rows ``X`` [S, n0] in one fused launch
+    (``fa_causal_kernel``, definitions in ops/causal.py): ``code`` uint8 [S, T] in the table's set
+    order, or ``None`` when the kernel does not cover the shape (a layer over 160 wide, over 32
+    inputs, more than 64 KB of LDS): the caller takes ``ops/causal.causal_codes_ref``.  ``table``: an
+    ``ops/causal.SetTable``.  ``blocks``: workgroups (default: one per work item, at most 1 024);
+    every value gives the same bytes.  The sets are launched by descending ``A_t``, so that the long
+    items start first."""
+    from .causal import MAX_DIMS, MAX_VALUE
+
+    if X.dim() != 2 or X.shape[1] != be.n0:
+        raise ValueError(f"X: expected [S, {be.n0}], got {tuple(X.shape)}")
+    S, T = int(X.shape[0]), table.T
+    dev = X.device
+    X = _c(X, torch.float32, (S, be.n0), "X")
+    if be.flat.device != dev:
+        raise ValueError("causal: X and the network must be on one device")
+    dims = np.ascontiguousarray(table.dims, dtype=np.int32)
+    vals = np.ascontiguousarray(table.vals, dtype=np.int32)
+    voff = np.ascontiguousarray(table.voff, dtype=np.int32)
+    if dims.ndim != 2 or dims.shape[1] != MAX_DIMS:
+        raise ValueError(f"causal: dims must be [T, {MAX_DIMS}], got {dims.shape}")
+    if voff.shape != (be.n0 + 1,) or voff[0] != 0 or voff[-1] != vals.size or (np.diff(voff) < 1).any():
+        raise ValueError(f"causal: voff must hold {be.n0 + 1} increasing offsets spanning vals")
+    if vals.size and int(np.abs(vals.astype(np.int64)).max()) > MAX_VALUE:
+        raise ValueError("causal: a value beyond +-2^24 (not exact in fp32)")
+    for t in range(T):
+        s = [int(d) for d in dims[t] if d != -1]
+        if not s or s != [int(d) for d in dims[t, :len(s)]] or any(not 0 <= d < be.n0 for d in s) \
+                or any(b <= a for a, b in zip(s, s[1:])):
+            raise ValueError(f"causal: set {dims[t].tolist()} is not a strictly increasing tuple padded with -1")
+    if blocks is None:
+        blocks = min(causal_items(S, T), _AUDIT_BLOCKS)
+    if not 1 <= int(blocks) <= causal_items(S, T):
+        raise ValueError(f"causal: {blocks} workgroups outside 1..{causal_items(S, T)}")
+    code = torch.zeros(S, T, dtype=torch.uint8, device=dev)
+    if max([be.n0] + list(be.widths)) > 160 or be.n0 > 32:
+        return None
+    if S and T:
+        order = np.argsort(-table.count.astype(np.int64), kind="stable")
+        ld = np.ascontiguousarray(dims[order])
+        out = torch.zeros(S, T, dtype=torch.uint8, device=dev)
+        tabs = dict(dims=torch.from_numpy(ld).to(dev), vals=torch.from_numpy(vals).to(dev),
+                    voff=torch.from_numpy(voff).to(dev))
+        ok = ext().causal(_net(be), **_ptrs(flat=be.flat, x=X, code=out, **tabs),
+                          S=S, T=T, D=MAX_DIMS, nvals=int(vals.size), set_dims=ld.reshape(-1).tolist(),
+                          value_off=voff.tolist(), blocks=int(blocks), stream=_stream(dev))
+        if not ok:
+            return None
+        code[:, torch.from_numpy(order).to(dev)] = out
+    return code
+
+
 # Workgroups of a leaf list: at least 1 024 (4 per CU), and enough that a workgroup enumerates about
 # _ENUM_POINTS points per staging of W -- leaves of 1 000 points measured 4 - 13 % faster one per
 # workgroup than eight per workgroup (profiles/r12/count/README.md); only small leaves share a workgroup
