@@ -115,6 +115,15 @@ def cmd_measure(args):
     print(json.dumps(out, indent=2, default=float))
 
 
+def cmd_gap(args):
+    from .analysis.gap import gap_preset
+
+    out = gap_preset(args.preset, args.model, results=args.results, tol=args.tol, node_budget=args.node_budget,
+                     leaf_points=args.leaf_points, max_partitions=args.max_partitions, seed=args.seed,
+                     weights=args.weights, device=_device(args.device), out_dir=args.out)
+    print(json.dumps(out, indent=2, default=float))
+
+
 def cmd_audit(args):
     from .analysis.audit import audit_preset
 
@@ -309,6 +318,28 @@ def main(argv=None):
                     help="--certify: open nodes of at most this many points are enumerated (<= 65536)")
     ms.add_argument("--out", default=None, help="directory for rate.csv / rate.json (and bounds.csv)")
     ms.set_defaults(fn=cmd_measure)
+
+    gp = sub.add_parser("gap", help="certified largest score gap between counterparts, per partition",
+                        description="Brackets, per partition, the largest |logit(x) - logit(x')| over the pairs the "
+                                    "query relates (gap_lo <= G <= gap_hi, units of the logit) with an exactly "
+                                    "evaluated witness pair.  FAIRIFY_GAP_FUSED=1 enumerates leaves with the fused GPU "
+                                    "kernel (networks with at most 32 inputs, layers up to 160 wide and 64 KB of LDS); "
+                                    "otherwise the composed path runs.  Writes gap.csv / gap.json.")
+    gp.add_argument("--preset", required=True)
+    gp.add_argument("--model", required=True)
+    gp.add_argument("--results", default=None,
+                    help="results dir of a verify run: maxima per verdict class; a witness that flips inside an "
+                         "UNSAT partition is a prover bug (SoundnessError)")
+    gp.add_argument("--tol", type=float, default=0.01, help="a node within this of the incumbent is pruned")
+    gp.add_argument("--node-budget", type=int, default=65536, help="nodes bounded per partition")
+    gp.add_argument("--leaf-points", type=int, default=1024,
+                    help="open nodes of at most this many points are enumerated (<= 65536)")
+    gp.add_argument("--max-partitions", type=int, default=None)
+    gp.add_argument("--seed", type=int, default=0)
+    gp.add_argument("--weights", default="zoo")
+    gp.add_argument("--device", default=None)
+    gp.add_argument("--out", required=True, help="directory for gap.csv / gap.json")
+    gp.set_defaults(fn=cmd_gap)
 
     au = sub.add_parser("audit", help="exact per-row discrimination flags of a table of individuals")
     au.add_argument("--preset", required=True)

@@ -566,6 +566,83 @@ struct EnumArgs {
   int blocks;               // workgroups (leaves strided over them)
 };
 
+// Score-gap leaf enumeration (csrc/gap.hip, definitions in ops/gap.py): the leaf boxes, tables and
+// point decode of EnumArgs; per point, pair and offset cert = max(lb' - ub, lb - ub') and poss =
+// max(ub' - lb, ub - lb') from the rigorous point bounds, each subtraction in fp64 and widened outward
+// by g1 times the operands' magnitudes.  Per leaf the largest cert with its argument (lowest point, then pair, then
+// offset on ties) and the largest poss.  No atomics on global memory.
+struct GapEnumArgs {
+  const float* flat;
+  const float* lo;          // [L, n0] leaf boxes (integral)
+  const float* hi;          // [L, n0]
+  int L;
+  int V;                    // PA assignments
+  int npa;
+  int pa_idx[FA_MAX_PA];
+  const int64_t* values;    // [V, npa]
+  int Pp;                   // valid ordered pairs (>= 1)
+  const int64_t* pairs;     // [Pp, 2]
+  int nra;                  // 0: PA-only query
+  int ra_idx[FA_MAX_RA];
+  int tau;
+  int E;                    // (2 tau + 1)^nra offset vectors (1 when nra == 0)
+  int max_vol;              // the caller's bound of a leaf's volume (<= FA_COUNT_MAX_VOL); a leaf over it
+                            // is not enumerated: arg_s = -2
+  double g1;                // gamma(1, FP64_UNIT) of the subtractions (set by the launch)
+  double* leaf_lo;          // [L] largest certain gap
+  double* leaf_hi;          // [L] largest possible gap
+  int* arg_s;               // [L] argument of leaf_lo: point, pair, offset (-1: no valid pair)
+  int* arg_pair;
+  int* arg_e;
+  int blocks;               // workgroups (leaves strided over them)
+};
+
+// Score-gap level step (csrc/gap.hip, definitions in ops/gap.py): a 16-lane group per node.  From the
+// logit forms of the node's V rows and counterpart rows: the coupled fp64 bound of every pair and
+// orientation, the node's ub (rounded up to fp32), best pair, code (0 PRUNED: ub <= thr[part], 1 LEAF,
+// 2 INNER), split dim, candidate rows; children and leaves go to lists whose slots are reserved with
+// one atomic per wave (the keys tell the caller the node order).
+struct GapLevelArgs {
+  int N, n0, V;
+  int npa;
+  int pa_idx[FA_MAX_PA];
+  int nra;
+  int ra_idx[FA_MAX_RA];
+  float tau;
+  const float* lo;          // [N, n0] node boxes
+  const float* hi;
+  const int* part;          // [N]
+  const float* values;      // [V, npa]
+  int Pp;
+  const int64_t* pairs;     // [Pp, 2]
+  const float *Lc, *L0, *Le, *Uc, *U0, *Ue, *lb, *ub;           // x rows [N V, n0] / [N V]
+  const float *Lcp, *L0p, *Lep, *Ucp, *U0p, *Uep, *lbp, *ubp;   // counterpart rows
+  const double* thr;        // [P] inc_start + tol
+  const float* score;       // [n0] s_d
+  long long leaf_points;
+  double gam, g1;           // gamma(2 n0 + 8, FP64_UNIT), gamma(1, FP64_UNIT) (set by the launch)
+  float* out_ub;            // [N]
+  uint8_t* code;            // [N]
+  int* best_pair;           // [N]
+  int* orient;              // [N] 0: A, 1: B
+  int* sdim;                // [N]
+  float* coef;              // [N, n0] fp32 c of the best pair (0 on PA dims)
+  float* cand_x;            // [N, n0]
+  float* cand_xp;           // [N, n0]
+  float* olo;               // child pool [cap, n0]
+  float* ohi;
+  int* opart;               // [cap]
+  float* oub;               // [cap] the parent's ub
+  int* okey;                // [cap] 2 k, 2 k + 1 for node k
+  int cap;
+  float* leaf_lo;           // leaf list [leaf_cap, n0]
+  float* leaf_hi;
+  int* leaf_part;           // [leaf_cap]
+  int* leaf_key;            // [leaf_cap] node index
+  int leaf_cap;
+  int* counters;            // [0] children, [1] leaves, [2] nodes that did not fit
+};
+
 // Row expansion and level step of the counting branch-and-bound: node k owns rows k V .. k V + V - 1
 // (its box with the PA dims pinned to values[v]); the counterpart rows are the same rows with every RA
 // dim widened by tau on both sides (relaxed queries only).

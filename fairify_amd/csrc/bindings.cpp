@@ -40,6 +40,8 @@ extern "C" int fa_audit_launch(const NetDesc& net, AuditArgs a, hipStream_t stre
 extern "C" int fa_neighbour_launch(const NetDesc& net, NeighbourArgs a, hipStream_t stream);
 extern "C" int fa_causal_launch(const NetDesc& net, CausalArgs a, hipStream_t stream);
 extern "C" int fa_count_enum_launch(const NetDesc& net, EnumArgs a, hipStream_t stream);
+extern "C" int fa_gap_enum_launch(const NetDesc& net, GapEnumArgs a, hipStream_t stream);
+extern "C" int fa_gap_level_launch(GapLevelArgs a, hipStream_t stream);
 extern "C" int fa_count_rows_launch(CountArgs a, hipStream_t stream);
 extern "C" int fa_count_level_launch(CountArgs a, hipStream_t stream);
 extern "C" int fa_ascent_launch(const NetDesc& net, AscentArgs a, hipStream_t stream);
@@ -636,6 +638,96 @@ PYBIND11_MODULE(_C, m) {
       throw std::invalid_argument(
           "count_enum: shape not covered (layer > 160, inputs > 32, V > 32, E > 32 or leaf volume > 65536)");
     ckl(rc, "count_enum");
+  });
+  // score-gap leaf enumeration (csrc/gap.hip): false when the kernel does not cover the shape
+  m.def("gap_enum", [](const Net& net, py::kwargs kw) {
+    Kw k("gap_enum", kw);
+    GapEnumArgs a{};
+    a.flat = k.need<const float>("flat");
+    a.lo = k.need<const float>("lo");
+    a.hi = k.need<const float>("hi");
+    a.L = k.i("L");
+    a.V = k.i("V");
+    a.npa = dims(k, "pa", a.pa_idx, FA_MAX_PA, "too many PA/RA dims");
+    a.values = k.need<const int64_t>("values");
+    a.Pp = k.i("Pp");
+    a.pairs = k.need<const int64_t>("pairs");
+    a.nra = dims(k, "ra", a.ra_idx, FA_MAX_RA, "too many PA/RA dims");
+    a.tau = k.i("tau");
+    a.E = k.i("E");
+    a.max_vol = k.i("max_vol");
+    a.leaf_lo = k.need<double>("leaf_lo");
+    a.leaf_hi = k.need<double>("leaf_hi");
+    a.arg_s = k.need<int>("arg_s");
+    a.arg_pair = k.need<int>("arg_pair");
+    a.arg_e = k.need<int>("arg_e");
+    a.blocks = k.i("blocks");
+    const int rc = fa_gap_enum_launch(net.d, a, finish(k));
+    if (rc == -3) return false;
+    if (rc == -2) throw std::invalid_argument("gap_enum: workgroup count outside 1..leaves");
+    ckl(rc, "gap_enum");
+    return true;
+  });
+  // score-gap level step (csrc/gap.hip): false when the kernel does not cover the shape
+  m.def("gap_level", [](py::kwargs kw) {
+    Kw k("gap_level", kw);
+    GapLevelArgs a{};
+    a.N = k.i("N");
+    a.n0 = k.i("n0");
+    a.V = k.i("V");
+    a.npa = dims(k, "pa", a.pa_idx, FA_MAX_PA, "too many PA/RA dims");
+    a.nra = dims(k, "ra", a.ra_idx, FA_MAX_RA, "too many PA/RA dims");
+    a.tau = k.f("tau");
+    a.lo = k.need<const float>("lo");
+    a.hi = k.need<const float>("hi");
+    a.part = k.need<const int>("part");
+    a.values = k.need<const float>("values");
+    a.Pp = k.i("Pp");
+    a.pairs = k.need<const int64_t>("pairs");
+    a.Lc = k.need<const float>("Lc");
+    a.L0 = k.need<const float>("L0");
+    a.Le = k.need<const float>("Le");
+    a.Uc = k.need<const float>("Uc");
+    a.U0 = k.need<const float>("U0");
+    a.Ue = k.need<const float>("Ue");
+    a.lb = k.need<const float>("lb");
+    a.ub = k.need<const float>("ub");
+    a.Lcp = k.need<const float>("Lcp");
+    a.L0p = k.need<const float>("L0p");
+    a.Lep = k.need<const float>("Lep");
+    a.Ucp = k.need<const float>("Ucp");
+    a.U0p = k.need<const float>("U0p");
+    a.Uep = k.need<const float>("Uep");
+    a.lbp = k.need<const float>("lbp");
+    a.ubp = k.need<const float>("ubp");
+    a.thr = k.need<const double>("thr");
+    a.score = k.need<const float>("score");
+    a.leaf_points = (long long)k.u64("leaf_points");
+    a.out_ub = k.need<float>("out_ub");
+    a.code = k.need<uint8_t>("code");
+    a.best_pair = k.need<int>("best_pair");
+    a.orient = k.need<int>("orient");
+    a.sdim = k.need<int>("sdim");
+    a.coef = k.need<float>("coef");
+    a.cand_x = k.need<float>("cand_x");
+    a.cand_xp = k.need<float>("cand_xp");
+    a.olo = k.need<float>("olo");
+    a.ohi = k.need<float>("ohi");
+    a.opart = k.need<int>("opart");
+    a.oub = k.need<float>("oub");
+    a.okey = k.need<int>("okey");
+    a.cap = k.i("cap");
+    a.leaf_lo = k.need<float>("leaf_lo");
+    a.leaf_hi = k.need<float>("leaf_hi");
+    a.leaf_part = k.need<int>("leaf_part");
+    a.leaf_key = k.need<int>("leaf_key");
+    a.leaf_cap = k.i("leaf_cap");
+    a.counters = k.need<int>("counters");
+    const int rc = fa_gap_level_launch(a, finish(k));
+    if (rc == -3) return false;
+    if (rc == -2) throw std::invalid_argument("gap_level: too many nodes in one launch");
+    ckl(rc, "gap_level");
+    return true;
   });
   // the block the row expansion and the level step share
   auto count_args = [](Kw& k) {

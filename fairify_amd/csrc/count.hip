@@ -11,8 +11,7 @@
 // The bound kernels (bounds.hip / symbolic.hip / crown.hip) run unchanged between the last two.
 #include <hip/hip_runtime.h>
 
-#include "pointfwd.h"
-#include "regfwd.h"
+#include "enumfwd.h"
 #include "wave.h"
 
 // ---- leaf enumeration ------------------------------------------------------------------------
@@ -45,26 +44,8 @@ fa_count_enum_kernel(NetDesc net, EnumArgs a, RegNetCfg rc, PointCfg cfg) {
     const int64_t vi = a.pairs[2 * q], vj = a.pairs[2 * q + 1];
     if (vi >= 0 && vi < V && vj >= 0 && vj < V) valid[(int)vi * V + (int)vj] = 1;
   }
-  // which PA dim (if any) each of this lane's input coordinates is, and the stride of its digit in
-  // the offset index (0: not an RA dim); fixed for the launch
-  int8_t pslot[XT][4];
-  int rstride[XT][4];
-  const int base = 2 * a.tau + 1;
-#pragma unroll
-  for (int t = 0; t < XT; ++t)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int k = 16 * t + 4 * grp + i;
-      int q = -1, rs = 0, st = 1;
-      for (int m = 0; m < a.npa; ++m)
-        if (a.pa_idx[m] == k) q = m;
-      for (int m = a.nra - 1; m >= 0; --m) {
-        if (a.ra_idx[m] == k) rs = st;
-        st *= base;
-      }
-      pslot[t][i] = (int8_t)q;
-      rstride[t][i] = rs;
-    }
+  FaEnumSlots<XT> slots;      // this lane's PA / RA slots, fixed for the launch
+  fa_enum_slots<XT>(a, grp, slots);
   BoundArgs ba{};
   ba.R = 16;
   const float g0 = net.g_fwd[0];
@@ -72,23 +53,10 @@ fa_count_enum_kernel(NetDesc net, EnumArgs a, RegNetCfg rc, PointCfg cfg) {
   for (int leaf = blockIdx.x; leaf < a.L; leaf += gridDim.x) {
     __syncthreads();     // the previous leaf's table and counter are no longer read
     if (tid == 0) {
-      // digit strides, last non-PA dim fastest; a PA dim has width 1 (its coordinate is overwritten)
-      long long vol = 1;
-      for (int k = n0 - 1; k >= 0; --k) {
-        const float l = a.lo[(size_t)leaf * n0 + k], h = a.hi[(size_t)leaf * n0 + k];
-        bool pa = false;
-        for (int m = 0; m < a.npa; ++m) pa = pa || a.pa_idx[m] == k;
-        const int w = pa ? 1 : (int)(h - l) + 1;
-        s_lo[k] = l;
-        s_w[k] = w;
-        s_st[k] = (int)vol;
-        if (w < 1) vol = 0;
-        if (vol <= a.max_vol) vol *= w;
-      }
-      const bool ok = vol >= 1 && vol <= a.max_vol;
+      const int v = fa_enum_decode(a, leaf, n0, s_lo, s_w, s_st);
       cnt[0] = 0;
-      cnt[1] = ok ? (int)vol : 0;
-      if (!ok) a.cert[leaf] = -1;
+      cnt[1] = v;
+      if (!v) a.cert[leaf] = -1;
     }
     __syncthreads();
     const int vol = cnt[1];
@@ -96,33 +64,10 @@ fa_count_enum_kernel(NetDesc net, EnumArgs a, RegNetCfg rc, PointCfg cfg) {
     for (int s0 = 0; s0 < vol; s0 += FA_THREADS / 4) {
       const int s = s0 + wave * 16 + col;
       const bool sv = s < vol;
-#pragma unroll
-      for (int t = 0; t < XT; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int k = 16 * t + 4 * grp + i;
-          Xb[t][i] = (k < n0 && sv) ? s_lo[k] + (float)((s / s_st[k]) % s_w[k]) : 0.f;
-        }
+      fa_enum_point<XT>(Xb, s, sv, grp, n0, s_lo, s_w, s_st);
       // rigorous forward of the 16 points' row (PA assignment v, offset vector e or -1) into slab row r
       auto run_row = [&](int v, int e, int r) {
-#pragma unroll
-        for (int t = 0; t < XT; ++t)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            float x = Xb[t][i];
-            const int q = pslot[t][i];
-            if (q >= 0) x = (float)a.values[v * a.npa + q];
-            const int rs = rstride[t][i];
-            if (e >= 0 && rs > 0) x += (float)((e / rs) % base - a.tau);
-            HA[t][i] = x;
-            EA[t][i] = g0 * fabsf(x);      // inputs are exact: only the GEMM rounding term
-          }
-        ba.out_lb = slab + r * 32;
-        ba.out_ub = slab + r * 32 + 16;
-        for (int l = 0; l < net.n_layers; ++l) {
-          if (l & 1) fa_point_layer<TM>(net, ba, cfg, smem, l, 0, lane, HB, EB, HA, EA);
-          else fa_point_layer<TM>(net, ba, cfg, smem, l, 0, lane, HA, EA, HB, EB);
-        }
+        fa_enum_run_row<TM, XT>(net, a, ba, cfg, smem, lane, Xb, slots, g0, v, e, slab + r * 32, HA, EA, HB, EB);
       };
       for (int v = 0; v < V; ++v) run_row(v, -1, v);
       // a slab row is written by lanes 0..15 and read back by the same lane only

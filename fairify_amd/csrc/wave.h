@@ -12,8 +12,8 @@ __device__ __forceinline__ float fa_gam(int k, float u) {
 }
 
 // butterfly sum within aligned groups of G lanes (every lane of the group gets the total)
-template <int G>
-__device__ __forceinline__ float fa_group_sum(float v) {
+template <int G, typename T>
+__device__ __forceinline__ T fa_group_sum(T v) {
 #pragma unroll
   for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
@@ -21,11 +21,11 @@ __device__ __forceinline__ float fa_group_sum(float v) {
 
 // (value, index) arg-max within aligned groups of G lanes (G = 64: the wave): the larger value wins,
 // ties go to the lower index (a sequential scan's first strict maximum); every lane gets the winner
-template <int G>
-__device__ __forceinline__ void fa_group_argmax(float& s, int& i) {
+template <int G, typename T>
+__device__ __forceinline__ void fa_group_argmax(T& s, int& i) {
 #pragma unroll
   for (int off = G / 2; off > 0; off >>= 1) {
-    const float s2 = __shfl_xor(s, off, 64);
+    const T s2 = __shfl_xor(s, off, 64);
     const int i2 = __shfl_xor(i, off, 64);
     if (s2 > s || (s2 == s && i2 < i)) { s = s2; i = i2; }
   }

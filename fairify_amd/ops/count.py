@@ -92,6 +92,13 @@ def split_ref(lo: torch.Tensor, hi: torch.Tensor, free, score: torch.Tensor):
     sc = w * score.to(lo.device, torch.float32)[f][None]
     sc = torch.where(w > 0, sc, torch.full_like(sc, -1.0))
     dim = f[sc.argmax(dim=1)] if N else torch.zeros(0, dtype=torch.long, device=lo.device)
+    return (dim,) + halves(lo, hi, dim)
+
+
+def halves(lo: torch.Tensor, hi: torch.Tensor, dim: torch.Tensor):
+    """Child boxes ``clo, chi`` [2 N, n] of nodes [N, n] halved along ``dim`` [N] (int64): node k's
+    children are rows 2k, 2k + 1."""
+    N, n = lo.shape
     ar = torch.arange(N, device=lo.device)
     l, h = lo[ar, dim], hi[ar, dim]
     m = l + torch.floor((h - l) / 2)
@@ -99,7 +106,7 @@ def split_ref(lo: torch.Tensor, hi: torch.Tensor, free, score: torch.Tensor):
     chi = hi[:, None, :].expand(N, 2, n).clone()
     chi[ar, 0, dim] = m
     clo[ar, 1, dim] = m + 1
-    return dim, clo.reshape(2 * N, n), chi.reshape(2 * N, n)
+    return clo.reshape(2 * N, n), chi.reshape(2 * N, n)
 
 
 def lattice_points_at(lo: torch.Tensor, hi: torch.Tensor, free, idx: torch.Tensor) -> torch.Tensor:

@@ -1148,6 +1148,114 @@ def count_enum(be, q, lo, hi, values, pairs, max_vol: Optional[int] = None, bloc
     return cert, amb, idx
 
 
+def gap_fused() -> bool:
+    """``FAIRIFY_GAP_FUSED=1`` (read per call) makes ``engine/gap.py`` run the level step and the
+    leaf enumeration on the kernels of csrc/gap.hip where they cover the shape; ``0`` or unset takes
+    the composed path -- ``ops/gap.level_ref``, materialised leaf points, ``point_bounds`` and the
+    torch reduction.  Opt-in: the kernel is 5 - 17 times faster on
+    the leaves alone, but the whole call gained 2 - 7 % in the median, inside its spread
+    (profiles/r21/gap/README.md)."""
+    return os.environ.get("FAIRIFY_GAP_FUSED", "0").strip() == "1"
+
+
+def gap_enum(be, q, lo, hi, values, pairs, max_vol: Optional[int] = None, blocks: Optional[int] = None):
+    """Score-gap leaf enumeration in one launch (``fa_gap_enum_kernel``, definitions in ops/gap.py):
+    (``leaf_lo`` [L] fp64, ``leaf_hi`` [L] fp64, ``arg_s``, ``arg_pair``, ``arg_e`` [L] int32), or
+    ``None`` when the kernel does not cover the shape (a layer over 160 wide, over 32 inputs, more
+    than 64 KB of LDS): the caller takes ``ops/gap.enum_gap_ref``.  ``max_vol``: the caller's bound of
+    the leaves' volumes (default: computed from the boxes; a leaf over it gets ``arg_s = -2``);
+    ``blocks``: workgroups (every value gives the same outputs)."""
+    from .count import MAX_LEAF_POINTS, free_dims, volumes
+
+    L, n0 = lo.shape
+    dev = lo.device
+    if n0 != be.n0:
+        raise ValueError(f"lo: expected [L, {be.n0}], got {tuple(lo.shape)}")
+    lo = _c(lo, torch.float32, (L, n0), "lo")
+    hi = _c(hi, torch.float32, (L, n0), "hi")
+    values = _c(values, torch.int64, None, "values")
+    pairs = _c(pairs, torch.int64, (pairs.shape[0], 2), "pairs")
+    V, Pp, E = _count_shape(be, q, values, pairs, "gap_enum")
+    if Pp < 1:
+        raise ValueError("gap_enum: no pair")
+    if max_vol is None:
+        max_vol = int(volumes(lo, hi, free_dims(q)).max()) if L else 1
+    if not 1 <= int(max_vol) <= MAX_LEAF_POINTS:
+        raise ValueError(f"gap_enum: leaf volume {max_vol} outside 1..{MAX_LEAF_POINTS}")
+    if blocks is None:
+        blocks = min(max(L, 1), max(_ENUM_BLOCKS, L * int(max_vol) // _ENUM_POINTS))
+    if L and not 1 <= int(blocks) <= L:
+        raise ValueError(f"gap_enum: {blocks} workgroups outside 1..{L}")
+    if max([be.n0] + list(be.widths)) > 160 or be.n0 > 32:
+        return None
+    leaf_lo = torch.zeros(L, dtype=torch.float64, device=dev)
+    leaf_hi = torch.zeros(L, dtype=torch.float64, device=dev)
+    arg = torch.full((3, L), -1, dtype=torch.int32, device=dev)
+    if L:
+        ok = ext().gap_enum(_net(be), **_ptrs(flat=be.flat, lo=lo, hi=hi, values=values, pairs=pairs, leaf_lo=leaf_lo,
+                                              leaf_hi=leaf_hi, arg_s=arg[0], arg_pair=arg[1], arg_e=arg[2]),
+                            L=L, V=V, pa=list(q.pa_idx), Pp=Pp, ra=list(q.ra_idx) if q.relaxed else [],
+                            tau=int(q.tau) if q.relaxed else 0, E=E, max_vol=int(max_vol), blocks=int(blocks),
+                            stream=_stream(dev))
+        if not ok:
+            return None
+    return leaf_lo, leaf_hi, arg[0], arg[1], arg[2]
+
+
+def gap_level(be, q, lo, hi, part, rx, rp, values, pairs, thr, score, leaf_points):
+    """Level step of the score-gap search over ``N`` nodes (``fa_gap_level_kernel``, definitions in
+    ops/gap.py) from the bound results ``rx`` / ``rp`` of the node rows [N V]: returns ``None`` when
+    the kernel does not cover the shape (over 32 inputs or PA assignments, no pair), else a dict with
+    ``ub`` [N] fp32, ``code`` [N] uint8, ``pair``, ``orient``, ``sdim`` [N] int32, ``c``, ``cand_x``,
+    ``cand_xp`` [N, n0], the child pool ``kids = (clo, chi, cpart, cub, ckey)`` (capacity 2 N), the
+    leaf list ``leaves = (llo, lhi, lpart, lkey)`` (capacity N) and ``counters`` [3] int32 on the
+    device (children, leaves, nodes that did not fit).  The lists are filled up to the counters in
+    atomic order; the keys (``2 k``, ``2 k + 1`` for the children of node ``k``, ``k`` for a leaf)
+    restore the node order.  ``thr`` [P] fp64: ``inc_start + tol``.  ``pairs`` is not
+    range-checked here (no synchronisation per launch): the kernel skips an index outside [0, V)."""
+    N, n0 = lo.shape
+    dev = lo.device
+    V, Pp = int(values.shape[0]), int(pairs.shape[0])
+    if n0 > 32 or not 1 <= V <= 32 or Pp < 1:
+        return None
+    lo = _c(lo, torch.float32, (N, n0), "lo")
+    hi = _c(hi, torch.float32, (N, n0), "hi")
+    part = _c(part, torch.int32, (N,), "part")
+    vals = _c(values, torch.float32, (V, len(q.pa_idx)), "values")
+    pairs = _c(pairs, torch.int64, (Pp, 2), "pairs")
+    thr = _c(thr, torch.float64, None, "thr")
+    score = _c(score.to(dev), torch.float32, (n0,), "score")
+    forms = {}
+    for r, sfx in ((rx, ""), (rp, "p")):
+        for name, t, shape in (("Lc", r.Lc, (N * V, n0)), ("L0", r.L0, (N * V,)), ("Le", r.Le, (N * V,)),
+                               ("Uc", r.Uc, (N * V, n0)), ("U0", r.U0, (N * V,)), ("Ue", r.Ue, (N * V,)),
+                               ("lb", r.out_lb, (N * V,)), ("ub", r.out_ub, (N * V,))):
+            forms[name + sfx] = _c(t, torch.float32, shape, name + sfx)
+    f32 = dict(dtype=torch.float32, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = dict(ub=torch.empty(N, **f32), code=torch.empty(N, dtype=torch.uint8, device=dev), pair=torch.empty(N, **i32),
+               orient=torch.empty(N, **i32), sdim=torch.empty(N, **i32), c=torch.zeros(N, n0, **f32),
+               cand_x=torch.empty(N, n0, **f32), cand_xp=torch.empty(N, n0, **f32))
+    kids = (torch.empty(2 * N, n0, **f32), torch.empty(2 * N, n0, **f32), torch.empty(2 * N, **i32),
+            torch.empty(2 * N, **f32), torch.empty(2 * N, **i32))
+    leaves = (torch.empty(N, n0, **f32), torch.empty(N, n0, **f32), torch.empty(N, **i32), torch.empty(N, **i32))
+    counters = torch.zeros(3, **i32)
+    if N:
+        ok = ext().gap_level(**_ptrs(lo=lo, hi=hi, part=part, values=vals, pairs=pairs, thr=thr, score=score,
+                                     out_ub=out["ub"], code=out["code"], best_pair=out["pair"], orient=out["orient"],
+                                     sdim=out["sdim"], coef=out["c"], cand_x=out["cand_x"], cand_xp=out["cand_xp"],
+                                     olo=kids[0], ohi=kids[1], opart=kids[2], oub=kids[3], okey=kids[4],
+                                     leaf_lo=leaves[0], leaf_hi=leaves[1], leaf_part=leaves[2], leaf_key=leaves[3],
+                                     counters=counters, **forms),
+                             N=N, n0=n0, V=V, pa=list(q.pa_idx), ra=list(q.ra_idx) if q.relaxed else [],
+                             tau=float(q.tau) if q.relaxed else 0.0, Pp=Pp, leaf_points=int(leaf_points), cap=2 * N,
+                             leaf_cap=N, stream=_stream(dev))
+        if not ok:
+            return None
+    out.update(kids=kids, leaves=leaves, counters=counters)
+    return out
+
+
 def count_rows(be, q, lo, hi, values):
     """Node boxes [N, n0] -> x rows ``rlo, rhi`` [N V, n0] and counterpart rows ``plo, phi`` (the x
     rows themselves for a PA-only query) via ``fa_count_rows_kernel`` (ops/count.py:node_rows)."""
