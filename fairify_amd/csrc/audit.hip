@@ -11,16 +11,13 @@
 //     own_sign      -1 if u < 0, +1 if l > 0, else 0.
 // The host decides the bits poss & ~cert exactly (engine/audit.py).
 //
-// Work shape (the rate kernel's, csrc/rate.hip): W staged once per workgroup in operand order with
-// the padded bias copy; each of the four waves owns 16 rows per pass = the 16 MFMA columns, and a
-// workgroup walks the 64-row passes blockIdx.x, blockIdx.x + gridDim.x, ...  The data flow differs:
+// Work shape: csrc/rowfwd.h; a workgroup walks the 64-row passes blockIdx.x, blockIdx.x + gridDim.x, ...
 // ONE x row per individual, forwarded once, its [l, u] kept in registers; every (v', e) counterpart
 // streams through the same forward into the wave's single slab row and is tested on the spot through
 // the V x V pair table in LDS, indexed by the column's own value.  Outputs are per row: no atomics.
 #include <hip/hip_runtime.h>
 
-#include "pointfwd.h"
-#include "regfwd.h"
+#include "rowfwd.h"
 
 // Waves per SIMD asked of the compiler, from its resource remarks (the table in docs/DESIGN.md 5f):
 // with at most 64 KB of LDS two workgroups fit a CU, and up to 7 tiles two waves per SIMD cost no
@@ -28,7 +25,7 @@
 // instance spills 356 B/lane at two waves and 12 B/lane at one, like the rate instance: one wave.
 template <int TM>
 __global__ void __launch_bounds__(FA_THREADS) __attribute__((amdgpu_waves_per_eu(TM == 10 ? 1 : 2)))
-fa_audit_kernel(NetDesc net, AuditArgs a, RegNetCfg rc, PointCfg cfg) {
+fa_audit_kernel(NetDesc net, AuditArgs a, RegNetCfg rc) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int XT = TM < 2 ? TM : 2;     // input tiles kept per row: n0 <= 32 (the launch refuses wider)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, grp = lane >> 4;
@@ -39,38 +36,12 @@ fa_audit_kernel(NetDesc net, AuditArgs a, RegNetCfg rc, PointCfg cfg) {
   float* slab = smem + rc.floats + wave * 32;
   uint8_t* valid = (uint8_t*)(smem + rc.floats + (FA_THREADS / 64) * 32);       // [V][V]
   fa_stage_wperm(net, rc, a.flat, smem, tid, FA_THREADS);
-  for (int i = tid; i < V * V; i += FA_THREADS) valid[i] = 0;
-  __syncthreads();
-  for (int q = tid; q < a.Pp; q += FA_THREADS) {
-    const int64_t vi = a.pairs[2 * q], vj = a.pairs[2 * q + 1];
-    if (vi >= 0 && vi < V && vj >= 0 && vj < V) valid[(int)vi * V + (int)vj] = 1;
-  }
-  __syncthreads();
-  // which PA dim (if any) each of this lane's input coordinates is, and the stride of its digit in
-  // the offset index (0: not an RA dim); fixed for the launch
-  int8_t pslot[XT][4];
-  int rstride[XT][4];
-  const int base = 2 * a.tau + 1;
-#pragma unroll
-  for (int t = 0; t < XT; ++t)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int k = 16 * t + 4 * grp + i;
-      int q = -1, rs = 0, st = 1;
-      for (int m = 0; m < a.npa; ++m)
-        if (a.pa_idx[m] == k) q = m;
-      for (int m = a.nra - 1; m >= 0; --m) {
-        if (a.ra_idx[m] == k) rs = st;
-        st *= base;
-      }
-      pslot[t][i] = (int8_t)q;
-      rstride[t][i] = rs;
-    }
+  fa_stage_pair_table(a, valid, tid);
+  FaRowSlots<XT> slots;       // this lane's PA / RA slots, fixed for the launch
+  fa_row_slots<XT>(a, grp, slots);
   // the layer function's view of the slab row: 16 points, lower bounds then upper bounds
   BoundArgs ba{};
   ba.R = 16;
-  ba.out_lb = slab;
-  ba.out_ub = slab + 16;
   const float g0 = net.g_fwd[0];
   float Xb[XT][4], HA[TM][4], EA[TM][4], HB[TM][4], EB[TM][4];
   const int passes = (a.N + 63) / 64;
@@ -90,22 +61,7 @@ fa_audit_kernel(NetDesc net, AuditArgs a, RegNetCfg rc, PointCfg cfg) {
     // rigorous forward of the 16 rows (PA assignment v or -1: the row's own, offset vector e or -1)
     // into the slab row
     auto run_row = [&](int v, int e) {
-#pragma unroll
-      for (int t = 0; t < XT; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float x = Xb[t][i];
-          const int q = pslot[t][i];
-          if (v >= 0 && q >= 0) x = (float)a.values[v * a.npa + q];
-          const int rs = rstride[t][i];
-          if (e >= 0 && rs > 0) x += (float)((e / rs) % base - a.tau);
-          HA[t][i] = x;
-          EA[t][i] = g0 * fabsf(x);      // inputs are exact: only the GEMM rounding term
-        }
-      for (int l = 0; l < net.n_layers; ++l) {
-        if (l & 1) fa_point_layer<TM>(net, ba, cfg, smem, l, 0, lane, HB, EB, HA, EA);
-        else fa_point_layer<TM>(net, ba, cfg, smem, l, 0, lane, HA, EA, HB, EB);
-      }
+      fa_row_forward<TM>(net, ba, rc, smem, lane, Xb, g0, FaQueryCoord<XT, AuditArgs>{a, slots, v, e}, slab, HA, EA, HB, EB);
     };
     run_row(-1, -1);
     // the slab row is written by lanes 0..15 and read back by the same lane only: the masks live in
@@ -138,18 +94,6 @@ fa_audit_kernel(NetDesc net, AuditArgs a, RegNetCfg rc, PointCfg cfg) {
   }
 }
 
-namespace {
-typedef void (*AuditKernel)(NetDesc, AuditArgs, RegNetCfg, PointCfg);
-AuditKernel select_audit(int TM) {
-  if (TM <= 1) return fa_audit_kernel<1>;
-  if (TM <= 2) return fa_audit_kernel<2>;
-  if (TM <= 4) return fa_audit_kernel<4>;
-  if (TM <= 7) return fa_audit_kernel<7>;
-  if (TM <= 10) return fa_audit_kernel<10>;
-  return nullptr;
-}
-}  // namespace
-
 // Dynamic LDS of one workgroup: the staged block, one slab row per wave, the pair table.
 static size_t audit_lds_bytes(const AuditArgs& a, const RegNetCfg& rc) {
   const size_t floats = (size_t)rc.floats + (size_t)(FA_THREADS / 64) * 32;
@@ -162,25 +106,20 @@ static size_t audit_lds_bytes(const AuditArgs& a, const RegNetCfg& rc) {
 // > 0 a HIP error.
 extern "C" int fa_audit_launch(const NetDesc& net, AuditArgs a, hipStream_t stream) {
   if (a.N <= 0) return 0;
-  if (a.npa < 1 || a.npa > FA_MAX_PA || a.nra < 0 || a.nra > FA_MAX_RA || a.tau < 0) return -3;
-  if (a.V < 1 || a.V > FA_RATE_MAX_V || a.E < 1 || a.E > FA_RATE_MAX_E || a.Pp < 0) return -3;
-  if (a.nra == 0 && a.E != 1) return -3;
-  for (int l = 0; l <= net.n_layers; ++l)
-    if (net.dims[l] > 160) return -3;
-  if (net.dims[0] > 32) return -3;
-  AuditKernel k = select_audit(fa_regnet_tm(net));
+  if (!fa_row_query_ok(net, a)) return -3;
   RegNetCfg rc{};
-  if (!k || !fa_regnet_cfg(net, rc)) return -3;
-  PointCfg cfg{};
-  for (int l = 0; l < net.n_layers; ++l) {
-    cfg.w_lds[l] = rc.w_lds[l];
-    cfg.b_lds[l] = rc.b_lds[l];
-    cfg.bp_lds[l] = rc.bp_lds[l];
+  void (*k)(NetDesc, AuditArgs, RegNetCfg) = nullptr;
+  switch (fa_row_net(net, rc)) {
+#define FA_AUDIT_CASE(T) \
+  case T: k = fa_audit_kernel<T>; break;
+    FA_ROW_TMS(FA_AUDIT_CASE)
+#undef FA_AUDIT_CASE
+    default: return -3;
   }
   const size_t bytes = audit_lds_bytes(a, rc);
   if (bytes > 64 * 1024) return -3;
   const int passes = (a.N + 63) / 64;
   if (a.blocks < 1 || a.blocks > passes) return -2;
-  hipLaunchKernelGGL(k, dim3((unsigned)a.blocks), dim3(FA_THREADS), bytes, stream, net, a, rc, cfg);
+  hipLaunchKernelGGL(k, dim3((unsigned)a.blocks), dim3(FA_THREADS), bytes, stream, net, a, rc);
   return (int)hipGetLastError();
 }

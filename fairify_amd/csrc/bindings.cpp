@@ -232,6 +232,30 @@ static void fill_ascent(A& a, Kw& k, const char* too_many) {
   a.wit_xp = k.need<float>("wit_xp");
 }
 
+// The query block of the row-forward kernels that take their rows or leaves from the caller (AuditArgs,
+// NeighbourArgs, EnumArgs, GapEnumArgs; csrc/rowfwd.h).  `pairs` may be absent when there is no pair,
+// unless `need_pairs`.
+template <typename A>
+static void fill_pairs(A& a, Kw& k, bool need_pairs = false) {
+  a.flat = k.need<const float>("flat");
+  a.V = k.i("V");
+  a.npa = dims(k, "pa", a.pa_idx, FA_MAX_PA, "too many PA/RA dims");
+  a.values = k.need<const int64_t>("values");
+  a.Pp = k.i("Pp");
+  a.pairs = (need_pairs || a.Pp > 0) ? k.need<const int64_t>("pairs") : k.ptr<const int64_t>("pairs");
+  a.nra = dims(k, "ra", a.ra_idx, FA_MAX_RA, "too many PA/RA dims");
+  a.tau = k.i("tau");
+  a.E = k.i("E");
+}
+// the PA / RA dims of a query lie inside the n0 inputs, or std::invalid_argument
+template <typename A>
+static void dims_inside(const char* fn, const A& a, int n0) {
+  for (int q = 0; q < a.npa; ++q)
+    if (a.pa_idx[q] < 0 || a.pa_idx[q] >= n0) throw std::invalid_argument(std::string(fn) + ": PA dim outside the inputs");
+  for (int q = 0; q < a.nra; ++q)
+    if (a.ra_idx[q] < 0 || a.ra_idx[q] >= n0) throw std::invalid_argument(std::string(fn) + ": RA dim outside the inputs");
+}
+
 // One beta level (BetaArgs; beta_level and the batched entry points share it).  `flags`: bit 0 stall,
 // bits 1-2 the primal-gap weights, bit 3 the infeasibility pass (ops/hip.py:beta_flags).
 static BetaArgs beta_args(const Net& net, Kw& k) {
@@ -499,28 +523,16 @@ PYBIND11_MODULE(_C, m) {
   m.def("audit", [](const Net& net, py::kwargs kw) {
     Kw k("audit", kw);
     AuditArgs a{};
-    a.flat = k.need<const float>("flat");
+    fill_pairs(a, k);
     a.x = k.need<const float>("x");
     a.own = k.need<const int>("own");
     a.N = k.i("N");
-    a.V = k.i("V");
-    a.npa = dims(k, "pa", a.pa_idx, FA_MAX_PA, "too many PA/RA dims");
-    a.values = k.need<const int64_t>("values");
-    a.Pp = k.i("Pp");
-    a.pairs = k.ptr<const int64_t>("pairs");
-    a.nra = dims(k, "ra", a.ra_idx, FA_MAX_RA, "too many PA/RA dims");
-    a.tau = k.i("tau");
-    a.E = k.i("E");
     a.cert = k.need<int>("cert");
     a.poss = k.need<int>("poss");
     a.own_sign = k.need<int8_t>("own_sign");
     a.blocks = k.i("blocks");
     if (a.N < 0) throw std::invalid_argument("audit: negative row count");
-    if (a.Pp > 0 && !a.pairs) throw py::type_error("audit() missing required keyword argument 'pairs'");
-    for (int q = 0; q < a.npa; ++q)
-      if (a.pa_idx[q] < 0 || a.pa_idx[q] >= net.d.dims[0]) throw std::invalid_argument("audit: PA dim outside the inputs");
-    for (int q = 0; q < a.nra; ++q)
-      if (a.ra_idx[q] < 0 || a.ra_idx[q] >= net.d.dims[0]) throw std::invalid_argument("audit: RA dim outside the inputs");
+    dims_inside("audit", a, net.d.dims[0]);
     const int rc = fa_audit_launch(net.d, a, finish(k));
     if (rc == -3) return false;
     if (rc == -2) throw std::invalid_argument("audit: workgroup count outside 1..number of 64-row passes");
@@ -533,18 +545,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("neighbours", [](const Net& net, py::kwargs kw) {
     Kw k("neighbours", kw);
     NeighbourArgs a{};
-    a.flat = k.need<const float>("flat");
+    fill_pairs(a, k);
     a.x = k.need<const float>("x");
     a.own = k.need<const int>("own");
     a.N = k.i("N");
-    a.V = k.i("V");
-    a.npa = dims(k, "pa", a.pa_idx, FA_MAX_PA, "too many PA/RA dims");
-    a.values = k.need<const int64_t>("values");
-    a.Pp = k.i("Pp");
-    a.pairs = k.ptr<const int64_t>("pairs");
-    a.nra = dims(k, "ra", a.ra_idx, FA_MAX_RA, "too many PA/RA dims");
-    a.tau = k.i("tau");
-    a.E = k.i("E");
     a.M = k.i("M");
     a.W = k.i("W");
     a.nb_dim = k.need<const int>("nb_dim");
@@ -558,13 +562,7 @@ PYBIND11_MODULE(_C, m) {
     a.blocks = k.i("blocks");
     if (a.N < 0 || a.M < 0) throw std::invalid_argument("neighbours: negative row or neighbour count");
     if (a.W != (a.M + 31) / 32) throw std::invalid_argument("neighbours: W is not ceil(M / 32)");
-    if (a.Pp > 0 && !a.pairs) throw py::type_error("neighbours() missing required keyword argument 'pairs'");
-    for (int q = 0; q < a.npa; ++q)
-      if (a.pa_idx[q] < 0 || a.pa_idx[q] >= net.d.dims[0])
-        throw std::invalid_argument("neighbours: PA dim outside the inputs");
-    for (int q = 0; q < a.nra; ++q)
-      if (a.ra_idx[q] < 0 || a.ra_idx[q] >= net.d.dims[0])
-        throw std::invalid_argument("neighbours: RA dim outside the inputs");
+    dims_inside("neighbours", a, net.d.dims[0]);
     const int rc = fa_neighbour_launch(net.d, a, finish(k));
     if (rc == -3) return false;
     if (rc == -2) throw std::invalid_argument("neighbours: workgroup count outside 1..passes x words");
@@ -615,24 +613,15 @@ PYBIND11_MODULE(_C, m) {
   m.def("count_enum", [](const Net& net, py::kwargs kw) {
     Kw k("count_enum", kw);
     EnumArgs a{};
-    a.flat = k.need<const float>("flat");
+    fill_pairs(a, k);
     a.lo = k.need<const float>("lo");
     a.hi = k.need<const float>("hi");
     a.L = k.i("L");
-    a.V = k.i("V");
-    a.npa = dims(k, "pa", a.pa_idx, FA_MAX_PA, "too many PA/RA dims");
-    a.values = k.need<const int64_t>("values");
-    a.Pp = k.i("Pp");
-    a.pairs = k.ptr<const int64_t>("pairs");
-    a.nra = dims(k, "ra", a.ra_idx, FA_MAX_RA, "too many PA/RA dims");
-    a.tau = k.i("tau");
-    a.E = k.i("E");
     a.max_vol = k.i("max_vol");
     a.cert = k.need<int>("cert");
     a.amb = k.need<int>("amb");
     a.amb_idx = k.need<int>("amb_idx");
     a.blocks = k.i("blocks");
-    if (a.Pp > 0 && !a.pairs) throw py::type_error("count_enum() missing required keyword argument 'pairs'");
     const int rc = fa_count_enum_launch(net.d, a, finish(k));
     if (rc == -3)
       throw std::invalid_argument(
@@ -643,18 +632,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("gap_enum", [](const Net& net, py::kwargs kw) {
     Kw k("gap_enum", kw);
     GapEnumArgs a{};
-    a.flat = k.need<const float>("flat");
+    fill_pairs(a, k, true);
     a.lo = k.need<const float>("lo");
     a.hi = k.need<const float>("hi");
     a.L = k.i("L");
-    a.V = k.i("V");
-    a.npa = dims(k, "pa", a.pa_idx, FA_MAX_PA, "too many PA/RA dims");
-    a.values = k.need<const int64_t>("values");
-    a.Pp = k.i("Pp");
-    a.pairs = k.need<const int64_t>("pairs");
-    a.nra = dims(k, "ra", a.ra_idx, FA_MAX_RA, "too many PA/RA dims");
-    a.tau = k.i("tau");
-    a.E = k.i("E");
     a.max_vol = k.i("max_vol");
     a.leaf_lo = k.need<double>("leaf_lo");
     a.leaf_hi = k.need<double>("leaf_hi");

@@ -12,8 +12,7 @@
 // code [S, T] holds one byte per (row, set): 0, 1 or 3.  The host decides the bytes equal to 1 exactly
 // (engine/causal.py).
 //
-// Work shape: the audit and neighbours kernels' (W staged once per workgroup, four waves, 16 rows per
-// wave = the 16 MFMA columns, one slab row per wave).  A work item is (64-row pass, set): items are
+// Work shape: csrc/rowfwd.h, one slab row per wave and no query.  A work item is (64-row pass, set): items are
 // strided over blockIdx.x, a set's passes side by side, so with the sets ordered by descending A_t the
 // long items start first.  The base row is bounded once per item; the assignments are walked
 // wave-uniformly with an odometer over the four digits (a padded slot has one value and always
@@ -21,13 +20,12 @@
 // No atomics.
 #include <hip/hip_runtime.h>
 
-#include "pointfwd.h"
-#include "regfwd.h"
+#include "rowfwd.h"
 
 // Waves per SIMD: the neighbours instances' values (docs/DESIGN.md 5h has the resource remarks).
 template <int TM>
 __global__ void __launch_bounds__(FA_THREADS) __attribute__((amdgpu_waves_per_eu(TM == 10 ? 1 : 2)))
-fa_causal_kernel(NetDesc net, CausalArgs a, RegNetCfg rc, PointCfg cfg) {
+fa_causal_kernel(NetDesc net, CausalArgs a, RegNetCfg rc) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int XT = TM < 2 ? TM : 2;     // input tiles kept per row: n0 <= 32 (the launch refuses wider)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, grp = lane >> 4;
@@ -63,6 +61,8 @@ fa_causal_kernel(NetDesc net, CausalArgs a, RegNetCfg rc, PointCfg cfg) {
       }
     // rigorous forward of the 16 columns' rows with the set's coordinates overwritten by v0 .. v3
     // (alter false: the base rows themselves), into the slab row
+    // (fa_row_forward's body, kept in place like rate.hip's: called as a function the 4-tile instance
+    // measured 5 % slower on AC-3, profiles/r22/rowfwd/README.md)
     auto run_row = [&](bool alter, float v0, float v1, float v2, float v3) {
 #pragma unroll
       for (int tt = 0; tt < XT; ++tt)
@@ -80,8 +80,8 @@ fa_causal_kernel(NetDesc net, CausalArgs a, RegNetCfg rc, PointCfg cfg) {
           EA[tt][i] = g0 * fabsf(x);      // inputs are exact: only the GEMM rounding term
         }
       for (int l = 0; l < net.n_layers; ++l) {
-        if (l & 1) fa_point_layer<TM>(net, ba, cfg, smem, l, 0, lane, HB, EB, HA, EA);
-        else fa_point_layer<TM>(net, ba, cfg, smem, l, 0, lane, HA, EA, HB, EB);
+        if (l & 1) fa_point_layer<TM>(net, ba, rc, smem, l, 0, lane, HB, EB, HA, EA);
+        else fa_point_layer<TM>(net, ba, rc, smem, l, 0, lane, HA, EA, HB, EB);
       }
     };
     run_row(false, 0.f, 0.f, 0.f, 0.f);
@@ -133,18 +133,6 @@ fa_causal_kernel(NetDesc net, CausalArgs a, RegNetCfg rc, PointCfg cfg) {
   }
 }
 
-namespace {
-typedef void (*CausalKernel)(NetDesc, CausalArgs, RegNetCfg, PointCfg);
-CausalKernel select_causal(int TM) {
-  if (TM <= 1) return fa_causal_kernel<1>;
-  if (TM <= 2) return fa_causal_kernel<2>;
-  if (TM <= 4) return fa_causal_kernel<4>;
-  if (TM <= 7) return fa_causal_kernel<7>;
-  if (TM <= 10) return fa_causal_kernel<10>;
-  return nullptr;
-}
-}  // namespace
-
 // Dynamic LDS of one workgroup: the staged block and one slab row per wave.
 static size_t causal_lds_bytes(const RegNetCfg& rc) {
   const size_t floats = (size_t)rc.floats + (size_t)(FA_THREADS / 64) * 32;
@@ -159,10 +147,10 @@ static size_t causal_lds_bytes(const RegNetCfg& rc) {
 extern "C" int fa_causal_launch(const NetDesc& net, CausalArgs a, hipStream_t stream) {
   if (a.S <= 0 || a.T <= 0) return 0;
   if (a.D != 4 || !a.h_dims || !a.h_voff) return -3;
-  for (int l = 0; l <= net.n_layers; ++l)
-    if (net.dims[l] > 160) return -3;
+  RegNetCfg rc{};
+  const int tmb = fa_row_net(net, rc);
+  if (!tmb) return -3;
   const int n0 = net.dims[0];
-  if (n0 > 32) return -3;
   if (a.h_voff[0] != 0 || a.h_voff[n0] != a.nvals) return -3;
   for (int k = 0; k < n0; ++k)
     if (a.h_voff[k + 1] <= a.h_voff[k]) return -3;
@@ -180,19 +168,18 @@ extern "C" int fa_causal_launch(const NetDesc& net, CausalArgs a, hipStream_t st
     }
     if (prev < 0) return -3;
   }
-  CausalKernel k = select_causal(fa_regnet_tm(net));
-  RegNetCfg rc{};
-  if (!k || !fa_regnet_cfg(net, rc)) return -3;
-  PointCfg cfg{};
-  for (int l = 0; l < net.n_layers; ++l) {
-    cfg.w_lds[l] = rc.w_lds[l];
-    cfg.b_lds[l] = rc.b_lds[l];
-    cfg.bp_lds[l] = rc.bp_lds[l];
+  void (*k)(NetDesc, CausalArgs, RegNetCfg) = nullptr;
+  switch (tmb) {
+#define FA_CAUSAL_CASE(T) \
+  case T: k = fa_causal_kernel<T>; break;
+    FA_ROW_TMS(FA_CAUSAL_CASE)
+#undef FA_CAUSAL_CASE
+    default: return -3;
   }
   const size_t bytes = causal_lds_bytes(rc);
   if (bytes > 64 * 1024) return -3;
   const long long items = (long long)((a.S + 63) / 64) * a.T;
   if (a.blocks < 1 || a.blocks > items) return -2;
-  hipLaunchKernelGGL(k, dim3((unsigned)a.blocks), dim3(FA_THREADS), bytes, stream, net, a, rc, cfg);
+  hipLaunchKernelGGL(k, dim3((unsigned)a.blocks), dim3(FA_THREADS), bytes, stream, net, a, rc);
   return (int)hipGetLastError();
 }

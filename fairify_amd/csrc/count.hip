@@ -2,26 +2,25 @@
 // 5e).  gfx950.
 //
 // fa_count_enum_kernel   leaf enumeration, the hot path: every lattice point of a small box is
-//                        classified like a discrimination-rate profile (csrc/rate.hip) -- the same
-//                        work shape and arithmetic, the coordinates from the leaf's mixed-radix
-//                        decode instead of the hash stream.
+//                        classified like a discrimination-rate profile (csrc/rate.hip), the
+//                        coordinates from the leaf's mixed-radix decode instead of the hash stream.
+//                        Work shape: csrc/rowfwd.h.
 // fa_count_rows_kernel   node boxes -> x rows (PA dims pinned) and widened counterpart rows.
 // fa_count_level_kernel  one node per lane: box test over the pair list, int64 volume sums, leaf
 //                        list and child pool slots reserved with one atomic per wave.
 // The bound kernels (bounds.hip / symbolic.hip / crown.hip) run unchanged between the last two.
 #include <hip/hip_runtime.h>
 
-#include "enumfwd.h"
+#include "rowfwd.h"
 #include "wave.h"
 
 // ---- leaf enumeration ------------------------------------------------------------------------
 // A workgroup walks the leaves blockIdx.x, blockIdx.x + gridDim.x, ...: W is staged once for many
-// small leaves.  Per leaf the widths and digit strides of its dims sit in LDS; a wave owns 16
-// points per pass = the 16 MFMA columns.  A leaf belongs to one workgroup, so its outputs do not
-// depend on the grid size.
+// small leaves.  Per leaf the widths and digit strides of its dims sit in LDS.  A leaf belongs to
+// one workgroup, so its outputs do not depend on the grid size.
 template <int TM>
 __global__ void __launch_bounds__(FA_THREADS) __attribute__((amdgpu_waves_per_eu(TM == 7 ? 2 : 1)))
-fa_count_enum_kernel(NetDesc net, EnumArgs a, RegNetCfg rc, PointCfg cfg) {
+fa_count_enum_kernel(NetDesc net, EnumArgs a, RegNetCfg rc) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int XT = TM < 2 ? TM : 2;     // input tiles kept per point: n0 <= 32 (the launch refuses wider)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, grp = lane >> 4;
@@ -38,14 +37,9 @@ fa_count_enum_kernel(NetDesc net, EnumArgs a, RegNetCfg rc, PointCfg cfg) {
   int* cnt = s_st + n0;                       // [0] certain points, [1] the leaf's volume (0: skipped)
   uint8_t* valid = (uint8_t*)(cnt + 2);       // [V][V]
   fa_stage_wperm(net, rc, a.flat, smem, tid, FA_THREADS);
-  for (int i = tid; i < V * V; i += FA_THREADS) valid[i] = 0;
-  __syncthreads();
-  for (int q = tid; q < a.Pp; q += FA_THREADS) {
-    const int64_t vi = a.pairs[2 * q], vj = a.pairs[2 * q + 1];
-    if (vi >= 0 && vi < V && vj >= 0 && vj < V) valid[(int)vi * V + (int)vj] = 1;
-  }
-  FaEnumSlots<XT> slots;      // this lane's PA / RA slots, fixed for the launch
-  fa_enum_slots<XT>(a, grp, slots);
+  fa_stage_pair_table(a, valid, tid);
+  FaRowSlots<XT> slots;       // this lane's PA / RA slots, fixed for the launch
+  fa_row_slots<XT>(a, grp, slots);
   BoundArgs ba{};
   ba.R = 16;
   const float g0 = net.g_fwd[0];
@@ -67,7 +61,8 @@ fa_count_enum_kernel(NetDesc net, EnumArgs a, RegNetCfg rc, PointCfg cfg) {
       fa_enum_point<XT>(Xb, s, sv, grp, n0, s_lo, s_w, s_st);
       // rigorous forward of the 16 points' row (PA assignment v, offset vector e or -1) into slab row r
       auto run_row = [&](int v, int e, int r) {
-        fa_enum_run_row<TM, XT>(net, a, ba, cfg, smem, lane, Xb, slots, g0, v, e, slab + r * 32, HA, EA, HB, EB);
+        fa_row_forward<TM>(net, ba, rc, smem, lane, Xb, g0, FaQueryCoord<XT, EnumArgs>{a, slots, v, e}, slab + r * 32, HA,
+                           EA, HB, EB);
       };
       for (int v = 0; v < V; ++v) run_row(v, -1, v);
       // a slab row is written by lanes 0..15 and read back by the same lane only
@@ -110,18 +105,6 @@ fa_count_enum_kernel(NetDesc net, EnumArgs a, RegNetCfg rc, PointCfg cfg) {
   }
 }
 
-namespace {
-typedef void (*EnumKernel)(NetDesc, EnumArgs, RegNetCfg, PointCfg);
-EnumKernel select_enum(int TM) {
-  if (TM <= 1) return fa_count_enum_kernel<1>;
-  if (TM <= 2) return fa_count_enum_kernel<2>;
-  if (TM <= 4) return fa_count_enum_kernel<4>;
-  if (TM <= 7) return fa_count_enum_kernel<7>;
-  if (TM <= 10) return fa_count_enum_kernel<10>;
-  return nullptr;
-}
-}  // namespace
-
 static size_t enum_lds_bytes(const NetDesc& net, const EnumArgs& a, const RegNetCfg& rc) {
   const size_t words = (size_t)rc.floats + (size_t)(FA_THREADS / 64) * (a.V + 1) * 32 + 3 * (size_t)net.dims[0] + 2;
   const size_t bytes = words * sizeof(float) + (size_t)a.V * a.V;
@@ -134,37 +117,28 @@ static size_t enum_lds_bytes(const NetDesc& net, const EnumArgs& a, const RegNet
 // dynamic-LDS limits were not prepared, > 0 a HIP error.
 extern "C" int fa_count_enum_launch(const NetDesc& net, EnumArgs a, hipStream_t stream) {
   if (a.L <= 0) return 0;
-  if (a.npa < 1 || a.npa > FA_MAX_PA || a.nra < 0 || a.nra > FA_MAX_RA || a.tau < 0) return -3;
-  if (a.V < 1 || a.V > FA_RATE_MAX_V || a.E < 1 || a.E > FA_RATE_MAX_E || a.Pp < 0) return -3;
-  if (a.nra == 0 && a.E != 1) return -3;
+  if (!fa_row_query_ok(net, a)) return -3;
   if (a.max_vol < 1 || a.max_vol > FA_COUNT_MAX_VOL) return -3;
-  for (int l = 0; l <= net.n_layers; ++l)
-    if (net.dims[l] > 160) return -3;
-  if (net.dims[0] > 32) return -3;
-  for (int m = 0; m < a.npa; ++m)
-    if (a.pa_idx[m] < 0 || a.pa_idx[m] >= net.dims[0]) return -3;
-  for (int m = 0; m < a.nra; ++m)
-    if (a.ra_idx[m] < 0 || a.ra_idx[m] >= net.dims[0]) return -3;
-  EnumKernel k = select_enum(fa_regnet_tm(net));
   RegNetCfg rc{};
-  if (!k || !fa_regnet_cfg(net, rc)) return -3;
-  PointCfg cfg{};
-  for (int l = 0; l < net.n_layers; ++l) {
-    cfg.w_lds[l] = rc.w_lds[l];
-    cfg.b_lds[l] = rc.b_lds[l];
-    cfg.bp_lds[l] = rc.bp_lds[l];
+  void (*k)(NetDesc, EnumArgs, RegNetCfg) = nullptr;
+  switch (fa_row_net(net, rc)) {
+#define FA_ENUM_CASE(T) \
+  case T: k = fa_count_enum_kernel<T>; break;
+    FA_ROW_TMS(FA_ENUM_CASE)
+#undef FA_ENUM_CASE
+    default: return -3;
   }
   const size_t bytes = enum_lds_bytes(net, a, rc);
   if (bytes > 160 * 1024) return -3;
   if (a.blocks < 1 || a.blocks > a.L) return -2;
   if (!fa_lds_ok(bytes)) return -4;
-  hipLaunchKernelGGL(k, dim3((unsigned)a.blocks), dim3(FA_THREADS), bytes, stream, net, a, rc, cfg);
+  hipLaunchKernelGGL(k, dim3((unsigned)a.blocks), dim3(FA_THREADS), bytes, stream, net, a, rc);
   return (int)hipGetLastError();
 }
 
-FA_LDS_REGISTER(FA_LDS_K(fa_count_enum_kernel<1>), FA_LDS_K(fa_count_enum_kernel<2>),
-                FA_LDS_K(fa_count_enum_kernel<4>), FA_LDS_K(fa_count_enum_kernel<7>),
-                FA_LDS_K(fa_count_enum_kernel<10>));
+#define FA_ENUM_LDS(T) FA_LDS_K(fa_count_enum_kernel<T>),
+FA_LDS_REGISTER(FA_ROW_TMS(FA_ENUM_LDS));
+#undef FA_ENUM_LDS
 
 // ---- row expansion ---------------------------------------------------------------------------
 // One thread per row element: row r = node r / V with PA assignment r % V.

@@ -1,6 +1,6 @@
 // Certified score gap between counterparts (definitions: ops/gap.py).  gfx950.
 //
-// fa_gap_enum_kernel   leaf enumeration, the hot path: the work shape and rigorous point forward of
+// fa_gap_enum_kernel   leaf enumeration, the hot path (work shape: csrc/rowfwd.h), over the leaves like
 //                      fa_count_enum_kernel (csrc/count.hip); instead of counting flags every point
 //                      reduces the certain / possible gap over pairs and offsets in registers, then an
 //                      arg-max (lowest point, pair, offset on ties) runs over the wave and across the
@@ -12,7 +12,7 @@
 
 #include <climits>
 
-#include "enumfwd.h"
+#include "rowfwd.h"
 #include "wave.h"
 
 // a - b in fp64, widened outward by g (|a| + |b|): the reference's separately rounded operations
@@ -28,7 +28,7 @@ __device__ __forceinline__ double fa_gap_hi(float a, float b, double g) {
 
 template <int TM>
 __global__ void __launch_bounds__(FA_THREADS) __attribute__((amdgpu_waves_per_eu(TM == 7 ? 2 : 1)))
-fa_gap_enum_kernel(NetDesc net, GapEnumArgs a, RegNetCfg rc, PointCfg cfg) {
+fa_gap_enum_kernel(NetDesc net, GapEnumArgs a, RegNetCfg rc) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int XT = TM < 2 ? TM : 2;     // input tiles kept per point: n0 <= 32 (the launch refuses wider)
   constexpr int NW = FA_THREADS / 64;
@@ -58,8 +58,8 @@ fa_gap_enum_kernel(NetDesc net, GapEnumArgs a, RegNetCfg rc, PointCfg cfg) {
   __syncthreads();
   for (int i = tid; i < V * V; i += FA_THREADS)
     if (pidx[i] == INT_MAX) pidx[i] = -1;
-  FaEnumSlots<XT> slots;      // this lane's PA / RA slots, fixed for the launch
-  fa_enum_slots<XT>(a, grp, slots);
+  FaRowSlots<XT> slots;       // this lane's PA / RA slots, fixed for the launch
+  fa_row_slots<XT>(a, grp, slots);
   BoundArgs ba{};
   ba.R = 16;
   const float g0 = net.g_fwd[0];
@@ -81,7 +81,8 @@ fa_gap_enum_kernel(NetDesc net, GapEnumArgs a, RegNetCfg rc, PointCfg cfg) {
       fa_enum_point<XT>(Xb, s, sv, grp, n0, s_lo, s_w, s_st);
       // rigorous forward of the 16 points' row (PA assignment v, offset vector e or -1) into slab row r
       auto run_row = [&](int v, int e, int r) {
-        fa_enum_run_row<TM, XT>(net, a, ba, cfg, smem, lane, Xb, slots, g0, v, e, slab + r * 32, HA, EA, HB, EB);
+        fa_row_forward<TM>(net, ba, rc, smem, lane, Xb, g0, FaQueryCoord<XT, GapEnumArgs>{a, slots, v, e}, slab + r * 32,
+                           HA, EA, HB, EB);
       };
       for (int v = 0; v < V; ++v) run_row(v, -1, v);
       // a slab row is written by lanes 0..15 and read back by the same lane only.  The point's own
@@ -168,18 +169,6 @@ fa_gap_enum_kernel(NetDesc net, GapEnumArgs a, RegNetCfg rc, PointCfg cfg) {
   }
 }
 
-namespace {
-typedef void (*GapEnumKernel)(NetDesc, GapEnumArgs, RegNetCfg, PointCfg);
-GapEnumKernel select_gap_enum(int TM) {
-  if (TM <= 1) return fa_gap_enum_kernel<1>;
-  if (TM <= 2) return fa_gap_enum_kernel<2>;
-  if (TM <= 4) return fa_gap_enum_kernel<4>;
-  if (TM <= 7) return fa_gap_enum_kernel<7>;
-  if (TM <= 10) return fa_gap_enum_kernel<10>;
-  return nullptr;
-}
-}  // namespace
-
 static size_t gap_enum_lds_bytes(const NetDesc& net, const GapEnumArgs& a, const RegNetCfg& rc) {
   const int NW = FA_THREADS / 64;
   const size_t words = (size_t)rc.floats + (size_t)NW * (a.V + 1) * 32 + 3 * (size_t)net.dims[0] + 2 + 7 * (size_t)NW +
@@ -192,32 +181,23 @@ static size_t gap_enum_lds_bytes(const NetDesc& net, const GapEnumArgs& a, const
 // bound over 65 536, more than 64 KB of LDS), -2 for a bad workgroup count, > 0 a HIP error.
 extern "C" int fa_gap_enum_launch(const NetDesc& net, GapEnumArgs a, hipStream_t stream) {
   if (a.L <= 0) return 0;
-  if (a.npa < 1 || a.npa > FA_MAX_PA || a.nra < 0 || a.nra > FA_MAX_RA || a.tau < 0) return -3;
-  if (a.V < 1 || a.V > FA_RATE_MAX_V || a.E < 1 || a.E > FA_RATE_MAX_E || a.Pp < 1) return -3;
-  if (a.nra == 0 && a.E != 1) return -3;
+  if (!fa_row_query_ok(net, a) || a.Pp < 1) return -3;
   if (a.max_vol < 1 || a.max_vol > FA_COUNT_MAX_VOL) return -3;
-  for (int l = 0; l <= net.n_layers; ++l)
-    if (net.dims[l] > 160) return -3;
-  if (net.dims[0] > 32) return -3;
-  for (int m = 0; m < a.npa; ++m)
-    if (a.pa_idx[m] < 0 || a.pa_idx[m] >= net.dims[0]) return -3;
-  for (int m = 0; m < a.nra; ++m)
-    if (a.ra_idx[m] < 0 || a.ra_idx[m] >= net.dims[0]) return -3;
-  GapEnumKernel k = select_gap_enum(fa_regnet_tm(net));
   RegNetCfg rc{};
-  if (!k || !fa_regnet_cfg(net, rc)) return -3;
-  PointCfg cfg{};
-  for (int l = 0; l < net.n_layers; ++l) {
-    cfg.w_lds[l] = rc.w_lds[l];
-    cfg.b_lds[l] = rc.b_lds[l];
-    cfg.bp_lds[l] = rc.bp_lds[l];
+  void (*k)(NetDesc, GapEnumArgs, RegNetCfg) = nullptr;
+  switch (fa_row_net(net, rc)) {
+#define FA_GAP_CASE(T) \
+  case T: k = fa_gap_enum_kernel<T>; break;
+    FA_ROW_TMS(FA_GAP_CASE)
+#undef FA_GAP_CASE
+    default: return -3;
   }
   const size_t bytes = gap_enum_lds_bytes(net, a, rc);
   if (bytes > 64 * 1024) return -3;
   const double ku = 3.0 * 0x1p-53;         // gamma(1, FP64_UNIT) as ops/reference.gamma rounds it
   a.g1 = ku / (1.0 - ku);
   if (a.blocks < 1 || a.blocks > a.L) return -2;
-  hipLaunchKernelGGL(k, dim3((unsigned)a.blocks), dim3(FA_THREADS), bytes, stream, net, a, rc, cfg);
+  hipLaunchKernelGGL(k, dim3((unsigned)a.blocks), dim3(FA_THREADS), bytes, stream, net, a, rc);
   return (int)hipGetLastError();
 }
 

@@ -12,22 +12,20 @@
 // Bit j sits in word j / 32 at bit j % 32 of cert / poss [N, W].  The host decides poss & ~cert
 // exactly (engine/neighbours.py).
 //
-// Work shape: the audit kernel's (W staged once per workgroup, four waves, 16 rows per wave = the 16
-// MFMA columns, one slab row per wave, the pair table in LDS).  A work item is (64-row pass, word):
+// Work shape: csrc/rowfwd.h, one slab row per wave like the audit kernel.  A work item is (64-row pass, word):
 // items are strided over blockIdx.x, so a short table of rows with a long neighbour table still
 // fills the device.  The up to 32 neighbours of a word are walked wave-uniformly; each grp == 0 lane
 // builds its row's two words in registers and stores them once.  No atomics.
 #include <hip/hip_runtime.h>
 
-#include "pointfwd.h"
-#include "regfwd.h"
+#include "rowfwd.h"
 
 // Waves per SIMD: the audit instances' values (docs/DESIGN.md 5g has the resource remarks of both).  No
 // scratch up to four tiles; the 7-tile instance spills 328 B/lane at two waves and 12 B/lane at one, and
 // measured 14 % faster at two (profiles/r19/neighbours/README.md).
 template <int TM>
 __global__ void __launch_bounds__(FA_THREADS) __attribute__((amdgpu_waves_per_eu(TM == 10 ? 1 : 2)))
-fa_neighbour_kernel(NetDesc net, NeighbourArgs a, RegNetCfg rc, PointCfg cfg) {
+fa_neighbour_kernel(NetDesc net, NeighbourArgs a, RegNetCfg rc) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int XT = TM < 2 ? TM : 2;     // input tiles kept per row: n0 <= 32 (the launch refuses wider)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, grp = lane >> 4;
@@ -36,36 +34,11 @@ fa_neighbour_kernel(NetDesc net, NeighbourArgs a, RegNetCfg rc, PointCfg cfg) {
   float* slab = smem + rc.floats + wave * 32;
   uint8_t* valid = (uint8_t*)(smem + rc.floats + (FA_THREADS / 64) * 32);       // [V][V]
   fa_stage_wperm(net, rc, a.flat, smem, tid, FA_THREADS);
-  for (int i = tid; i < V * V; i += FA_THREADS) valid[i] = 0;
-  __syncthreads();
-  for (int q = tid; q < a.Pp; q += FA_THREADS) {
-    const int64_t vi = a.pairs[2 * q], vj = a.pairs[2 * q + 1];
-    if (vi >= 0 && vi < V && vj >= 0 && vj < V) valid[(int)vi * V + (int)vj] = 1;
-  }
-  __syncthreads();
-  // PA slot and offset-digit stride of each of this lane's input coordinates (csrc/audit.hip)
-  int8_t pslot[XT][4];
-  int rstride[XT][4];
-  const int base = 2 * a.tau + 1;
-#pragma unroll
-  for (int t = 0; t < XT; ++t)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int k = 16 * t + 4 * grp + i;
-      int q = -1, rs = 0, st = 1;
-      for (int m = 0; m < a.npa; ++m)
-        if (a.pa_idx[m] == k) q = m;
-      for (int m = a.nra - 1; m >= 0; --m) {
-        if (a.ra_idx[m] == k) rs = st;
-        st *= base;
-      }
-      pslot[t][i] = (int8_t)q;
-      rstride[t][i] = rs;
-    }
+  fa_stage_pair_table(a, valid, tid);
+  FaRowSlots<XT> slots;       // this lane's PA / RA slots, fixed for the launch
+  fa_row_slots<XT>(a, grp, slots);
   BoundArgs ba{};
   ba.R = 16;
-  ba.out_lb = slab;
-  ba.out_ub = slab + 16;
   const float g0 = net.g_fwd[0];
   float Xb[XT][4], HA[TM][4], EA[TM][4], HB[TM][4], EB[TM][4];
   const int passes = (a.N + 63) / 64;
@@ -88,23 +61,12 @@ fa_neighbour_kernel(NetDesc net, NeighbourArgs a, RegNetCfg rc, PointCfg cfg) {
     // when relative), with PA assignment v (-1: the row's own) and offset vector e (-1: none), into
     // the slab row
     auto run_row = [&](int kd, float cf, bool isabs, int v, int e) {
-#pragma unroll
-      for (int t = 0; t < XT; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float x = Xb[t][i];
-          if (16 * t + 4 * grp + i == kd) x = isabs ? cf : x + cf;
-          const int q = pslot[t][i];
-          if (v >= 0 && q >= 0) x = (float)a.values[v * a.npa + q];
-          const int rs = rstride[t][i];
-          if (e >= 0 && rs > 0) x += (float)((e / rs) % base - a.tau);
-          HA[t][i] = x;
-          EA[t][i] = g0 * fabsf(x);      // inputs are exact: only the GEMM rounding term
-        }
-      for (int l = 0; l < net.n_layers; ++l) {
-        if (l & 1) fa_point_layer<TM>(net, ba, cfg, smem, l, 0, lane, HB, EB, HA, EA);
-        else fa_point_layer<TM>(net, ba, cfg, smem, l, 0, lane, HA, EA, HB, EB);
-      }
+      const FaQueryCoord<XT, NeighbourArgs> query{a, slots, v, e};
+      auto coord = [&](int t, int i, float x) {
+        if (16 * t + 4 * grp + i == kd) x = isabs ? cf : x + cf;
+        return query(t, i, x);
+      };
+      fa_row_forward<TM>(net, ba, rc, smem, lane, Xb, g0, coord, slab, HA, EA, HB, EB);
     };
     unsigned cw = 0, pw = 0;
     const int j1 = min(a.M, 32 * w + 32);
@@ -154,18 +116,6 @@ fa_neighbour_kernel(NetDesc net, NeighbourArgs a, RegNetCfg rc, PointCfg cfg) {
   }
 }
 
-namespace {
-typedef void (*NeighbourKernel)(NetDesc, NeighbourArgs, RegNetCfg, PointCfg);
-NeighbourKernel select_neighbour(int TM) {
-  if (TM <= 1) return fa_neighbour_kernel<1>;
-  if (TM <= 2) return fa_neighbour_kernel<2>;
-  if (TM <= 4) return fa_neighbour_kernel<4>;
-  if (TM <= 7) return fa_neighbour_kernel<7>;
-  if (TM <= 10) return fa_neighbour_kernel<10>;
-  return nullptr;
-}
-}  // namespace
-
 // Dynamic LDS of one workgroup: the staged block, one slab row per wave, the pair table.
 static size_t neighbour_lds_bytes(const NeighbourArgs& a, const RegNetCfg& rc) {
   const size_t floats = (size_t)rc.floats + (size_t)(FA_THREADS / 64) * 32;
@@ -178,26 +128,20 @@ static size_t neighbour_lds_bytes(const NeighbourArgs& a, const RegNetCfg& rc) {
 // workgroup count outside 1 .. passes x W, > 0 a HIP error.
 extern "C" int fa_neighbour_launch(const NetDesc& net, NeighbourArgs a, hipStream_t stream) {
   if (a.N <= 0 || a.M <= 0) return 0;
-  if (a.npa < 1 || a.npa > FA_MAX_PA || a.nra < 0 || a.nra > FA_MAX_RA || a.tau < 0) return -3;
-  if (a.V < 1 || a.V > FA_RATE_MAX_V || a.E < 1 || a.E > FA_RATE_MAX_E || a.Pp < 0) return -3;
-  if (a.nra == 0 && a.E != 1) return -3;
-  if (a.W != (a.M + 31) / 32) return -3;
-  for (int l = 0; l <= net.n_layers; ++l)
-    if (net.dims[l] > 160) return -3;
-  if (net.dims[0] > 32) return -3;
-  NeighbourKernel k = select_neighbour(fa_regnet_tm(net));
+  if (!fa_row_query_ok(net, a) || a.W != (a.M + 31) / 32) return -3;
   RegNetCfg rc{};
-  if (!k || !fa_regnet_cfg(net, rc)) return -3;
-  PointCfg cfg{};
-  for (int l = 0; l < net.n_layers; ++l) {
-    cfg.w_lds[l] = rc.w_lds[l];
-    cfg.b_lds[l] = rc.b_lds[l];
-    cfg.bp_lds[l] = rc.bp_lds[l];
+  void (*k)(NetDesc, NeighbourArgs, RegNetCfg) = nullptr;
+  switch (fa_row_net(net, rc)) {
+#define FA_NEIGHBOUR_CASE(T) \
+  case T: k = fa_neighbour_kernel<T>; break;
+    FA_ROW_TMS(FA_NEIGHBOUR_CASE)
+#undef FA_NEIGHBOUR_CASE
+    default: return -3;
   }
   const size_t bytes = neighbour_lds_bytes(a, rc);
   if (bytes > 64 * 1024) return -3;
   const long long items = (long long)((a.N + 63) / 64) * a.W;
   if (a.blocks < 1 || a.blocks > items) return -2;
-  hipLaunchKernelGGL(k, dim3((unsigned)a.blocks), dim3(FA_THREADS), bytes, stream, net, a, rc, cfg);
+  hipLaunchKernelGGL(k, dim3((unsigned)a.blocks), dim3(FA_THREADS), bytes, stream, net, a, rc);
   return (int)hipGetLastError();
 }

@@ -15,17 +15,14 @@
 // FA_RATE_SLOTS of their sample indices (slots reserved with an integer atomic; the host decides
 // those profiles exactly, engine/rate.py).  Integer atomics only: the counts are deterministic.
 //
-// Work shape (the simulation kernel's, csrc/forward.hip): a.split workgroups per partition, each
-// wave owns 16 profiles per pass = the 16 MFMA columns; W staged once per workgroup in operand
-// order with the padded bias copy.  Per pass the V x rows are forwarded first and their [l, u] kept
-// in a wave-private LDS slab; then (relaxed) the E*V counterpart rows stream through the same
-// forward into one more slab row and are tested on the spot against the stored x bounds through a
-// V x V pair-validity table in LDS -- nothing of size E*V is stored.  PA-only: the stored rows are
-// tested against each other, one pass.
+// Work shape: csrc/rowfwd.h, with a.split workgroups per partition.  Per pass the V x rows are
+// forwarded first and their [l, u] kept in a wave-private LDS slab; then (relaxed) the E*V counterpart
+// rows stream through the same forward into one more slab row and are tested on the spot against the
+// stored x bounds -- nothing of size E*V is stored.  PA-only: the stored rows are tested against each
+// other, one pass.
 #include <hip/hip_runtime.h>
 
-#include "pointfwd.h"
-#include "regfwd.h"
+#include "rowfwd.h"
 
 // 7-tile nets: two waves per SIMD like the point kernel (two AC-4 workgroups fit a CU's LDS), with
 // 120 B/lane of scratch; one wave per SIMD measured slower (AC-4: 15.8 against 11.4 ms,
@@ -36,7 +33,7 @@
 
 template <int TM>
 __global__ void __launch_bounds__(FA_THREADS) __attribute__((amdgpu_waves_per_eu(TM == 7 ? FA_RATE_WPE7 : 1)))
-fa_rate_kernel(NetDesc net, RateArgs a, RegNetCfg rc, PointCfg cfg) {
+fa_rate_kernel(NetDesc net, RateArgs a, RegNetCfg rc) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int XT = TM < 2 ? TM : 2;     // input tiles kept per profile: n0 <= 32 (the launch refuses wider)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, grp = lane >> 4;
@@ -59,34 +56,10 @@ fa_rate_kernel(NetDesc net, RateArgs a, RegNetCfg rc, PointCfg cfg) {
     s_lo[i] = a.lo[(size_t)p * n0 + i];
     s_hi[i] = a.hi[(size_t)p * n0 + i];
   }
-  for (int i = tid; i < V * V; i += FA_THREADS) valid[i] = 0;
   if (tid == 0) cnt[0] = 0;
-  __syncthreads();
-  for (int q = tid; q < a.Pp; q += FA_THREADS) {
-    const int64_t vi = a.pairs[2 * q], vj = a.pairs[2 * q + 1];
-    if (vi >= 0 && vi < V && vj >= 0 && vj < V) valid[(int)vi * V + (int)vj] = 1;
-  }
-  __syncthreads();
-  // which PA dim (if any) each of this lane's input coordinates is, and the stride of its digit in
-  // the offset index (0: not an RA dim); fixed for the launch
-  int8_t pslot[XT][4];
-  int rstride[XT][4];
-  const int base = 2 * a.tau + 1;
-#pragma unroll
-  for (int t = 0; t < XT; ++t)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int k = 16 * t + 4 * grp + i;
-      int q = -1, rs = 0, st = 1;
-      for (int m = 0; m < a.npa; ++m)
-        if (a.pa_idx[m] == k) q = m;
-      for (int m = a.nra - 1; m >= 0; --m) {
-        if (a.ra_idx[m] == k) rs = st;
-        st *= base;
-      }
-      pslot[t][i] = (int8_t)q;
-      rstride[t][i] = rs;
-    }
+  fa_stage_pair_table(a, valid, tid);
+  FaRowSlots<XT> slots;       // this lane's PA / RA slots, fixed for the launch
+  fa_row_slots<XT>(a, grp, slots);
   // the layer function's view of one slab row: 16 points, lower bounds then upper bounds
   BoundArgs ba{};
   ba.R = 16;
@@ -104,24 +77,23 @@ fa_rate_kernel(NetDesc net, RateArgs a, RegNetCfg rc, PointCfg cfg) {
         Xb[t][i] = (k < n0 && sv) ? fa_sample_coord(a.seed, pid, s, k, s_lo[k], s_hi[k]) : 0.f;
       }
     // rigorous forward of the 16 profiles' row (PA assignment v, offset vector e or -1) into slab row r
+    // (fa_row_forward's body, kept in place: called as a function, the 1-tile instance took two more
+    // VGPRs and lost its sixth wave per SIMD, profiles/r22/rowfwd/README.md)
     auto run_row = [&](int v, int e, int r) {
+      const FaQueryCoord<XT, RateArgs> coord{a, slots, v, e};
 #pragma unroll
       for (int t = 0; t < XT; ++t)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          float x = Xb[t][i];
-          const int q = pslot[t][i];
-          if (q >= 0) x = (float)a.values[v * a.npa + q];
-          const int rs = rstride[t][i];
-          if (e >= 0 && rs > 0) x += (float)((e / rs) % base - a.tau);
+          const float x = coord(t, i, Xb[t][i]);
           HA[t][i] = x;
           EA[t][i] = g0 * fabsf(x);      // inputs are exact: only the GEMM rounding term
         }
       ba.out_lb = slab + r * 32;
       ba.out_ub = slab + r * 32 + 16;
       for (int l = 0; l < net.n_layers; ++l) {
-        if (l & 1) fa_point_layer<TM>(net, ba, cfg, smem, l, 0, lane, HB, EB, HA, EA);
-        else fa_point_layer<TM>(net, ba, cfg, smem, l, 0, lane, HA, EA, HB, EB);
+        if (l & 1) fa_point_layer<TM>(net, ba, rc, smem, l, 0, lane, HB, EB, HA, EA);
+        else fa_point_layer<TM>(net, ba, rc, smem, l, 0, lane, HA, EA, HB, EB);
       }
     };
     for (int v = 0; v < V; ++v) run_row(v, -1, v);
@@ -164,18 +136,6 @@ fa_rate_kernel(NetDesc net, RateArgs a, RegNetCfg rc, PointCfg cfg) {
   if (tid == 0 && cnt[0]) atomicAdd(&a.flips[p], cnt[0]);
 }
 
-namespace {
-typedef void (*RateKernel)(NetDesc, RateArgs, RegNetCfg, PointCfg);
-RateKernel select_rate(int TM) {
-  if (TM <= 1) return fa_rate_kernel<1>;
-  if (TM <= 2) return fa_rate_kernel<2>;
-  if (TM <= 4) return fa_rate_kernel<4>;
-  if (TM <= 7) return fa_rate_kernel<7>;
-  if (TM <= 10) return fa_rate_kernel<10>;
-  return nullptr;
-}
-}  // namespace
-
 // Dynamic LDS of one workgroup, or 0 when the shape is not covered.
 static size_t rate_lds_bytes(const NetDesc& net, const RateArgs& a, const RegNetCfg& rc) {
   const size_t floats = (size_t)rc.floats + (size_t)(FA_THREADS / 64) * (a.V + 1) * 32 + 2 * (size_t)net.dims[0];
@@ -189,20 +149,15 @@ static size_t rate_lds_bytes(const NetDesc& net, const RateArgs& a, const RegNet
 // the dynamic-LDS limits were not prepared, > 0 a HIP error.
 extern "C" int fa_rate_launch(const NetDesc& net, RateArgs a, hipStream_t stream) {
   if (a.P <= 0 || a.n_samples <= 0) return 0;
-  if (a.npa < 1 || a.npa > FA_MAX_PA || a.nra < 0 || a.nra > FA_MAX_RA || a.tau < 0) return -3;
-  if (a.V < 1 || a.V > FA_RATE_MAX_V || a.E < 1 || a.E > FA_RATE_MAX_E || a.Pp < 0) return -3;
-  if (a.nra == 0 && a.E != 1) return -3;
-  for (int l = 0; l <= net.n_layers; ++l)
-    if (net.dims[l] > 160) return -3;
-  if (net.dims[0] > 32) return -3;
-  RateKernel k = select_rate(fa_regnet_tm(net));
+  if (!fa_row_query_ok(net, a)) return -3;
   RegNetCfg rc{};
-  if (!k || !fa_regnet_cfg(net, rc)) return -3;
-  PointCfg cfg{};
-  for (int l = 0; l < net.n_layers; ++l) {
-    cfg.w_lds[l] = rc.w_lds[l];
-    cfg.b_lds[l] = rc.b_lds[l];
-    cfg.bp_lds[l] = rc.bp_lds[l];
+  void (*k)(NetDesc, RateArgs, RegNetCfg) = nullptr;
+  switch (fa_row_net(net, rc)) {
+#define FA_RATE_CASE(T) \
+  case T: k = fa_rate_kernel<T>; break;
+    FA_ROW_TMS(FA_RATE_CASE)
+#undef FA_RATE_CASE
+    default: return -3;
   }
   const size_t bytes = rate_lds_bytes(net, a, rc);
   if (bytes > 160 * 1024) return -3;
@@ -210,9 +165,10 @@ extern "C" int fa_rate_launch(const NetDesc& net, RateArgs a, hipStream_t stream
   if (a.split < 1 || a.split > tiles) return -2;
   if ((long long)a.P * a.split > 0x7FFFFFFFLL) return -2;
   if (!fa_lds_ok(bytes)) return -4;
-  hipLaunchKernelGGL(k, dim3((unsigned)a.P * (unsigned)a.split), dim3(FA_THREADS), bytes, stream, net, a, rc, cfg);
+  hipLaunchKernelGGL(k, dim3((unsigned)a.P * (unsigned)a.split), dim3(FA_THREADS), bytes, stream, net, a, rc);
   return (int)hipGetLastError();
 }
 
-FA_LDS_REGISTER(FA_LDS_K(fa_rate_kernel<1>), FA_LDS_K(fa_rate_kernel<2>), FA_LDS_K(fa_rate_kernel<4>),
-                FA_LDS_K(fa_rate_kernel<7>), FA_LDS_K(fa_rate_kernel<10>));
+#define FA_RATE_LDS(T) FA_LDS_K(fa_rate_kernel<T>),
+FA_LDS_REGISTER(FA_ROW_TMS(FA_RATE_LDS));
+#undef FA_RATE_LDS

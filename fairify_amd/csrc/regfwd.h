@@ -8,12 +8,11 @@
 // 16-byte ds_read per lane per 4 MFMAs.
 #pragma once
 #include "args.h"
+#include "pointfwd.h"
 
-// LDS float offsets of each layer's permuted W and bias inside the staged block.
-struct RegNetCfg {
-  int w_lds[FA_MAX_LAYERS];
-  int b_lds[FA_MAX_LAYERS];
-  int bp_lds[FA_MAX_LAYERS];  // the layer's biases again, zero padded to whole 16-neuron tiles (16-byte aligned)
+// LDS float offsets of each layer's permuted W and bias inside the staged block (PointCfg: the rigorous
+// layer function fa_point_layer takes a RegNetCfg as it is), and the block's size.
+struct RegNetCfg : PointCfg {
   int floats;                 // staged LDS floats: the block (net.wperm_floats), then the padded biases
 };
 

@@ -819,6 +819,50 @@ def simulate(be, q, lo, hi, pids, n_samples, seed, values, pairs, bisect_pairs, 
     return res
 
 
+def _rowfwd_covers(be) -> bool:
+    """The net shape of the row-forward kernels (csrc/rowfwd.h): no layer over 160 wide, at most 32 inputs."""
+    return max([be.n0] + list(be.widths)) <= 160 and be.n0 <= 32
+
+
+def _pairs_kw(q, E: int) -> dict:
+    """The ``pa`` / ``ra`` / ``tau`` / ``E`` keywords of the bindings that take a query (RA dims and tau
+    only of a relaxed one)."""
+    return dict(pa=list(q.pa_idx), ra=list(q.ra_idx) if q.relaxed else [], tau=int(q.tau) if q.relaxed else 0, E=E)
+
+
+def _row_inputs(be, q, X, own, values, pairs, what):
+    """Checks of the rows, own indices and PA tables that ``audit_masks`` and ``neighbour_masks`` share:
+    the checked contiguous ``(X, own, values, pairs)`` and ``(N, V, Pp, E)``."""
+    from .audit import MAX_VALUES
+    from .rate import MAX_OFFSETS, offset_vectors
+
+    if X.dim() != 2 or X.shape[1] != be.n0:
+        raise ValueError(f"X: expected [N, {be.n0}], got {tuple(X.shape)}")
+    N = int(X.shape[0])
+    dev = X.device
+    npa = len(q.pa_idx)
+    if values.dim() != 2 or values.shape[1] != npa:
+        raise ValueError(f"values: expected [V, {npa}], got {tuple(values.shape)}")
+    V, Pp = int(values.shape[0]), int(pairs.shape[0])
+    if not 1 <= V <= MAX_VALUES:
+        raise ValueError(f"{what}: {V} PA assignments, the kernel covers 1..{MAX_VALUES}")
+    X = _c(X, torch.float32, (N, be.n0), "X")
+    own = _c(own, torch.int32, (N,), "own")
+    values = _c(values, torch.int64, (V, npa), "values")
+    pairs = _c(pairs, torch.int64, (Pp, 2), "pairs")
+    if any(t.device != dev for t in (own, values, pairs, be.flat)):
+        raise ValueError(f"{what}: X, own, values, pairs and the network must be on one device")
+    if Pp and (int(pairs.min()) < 0 or int(pairs.max()) >= V):
+        raise ValueError("pairs: index outside [0, V)")
+    if N:
+        omin, omax = torch.stack(torch.aminmax(own)).tolist()           # one read-back
+        if omin < -1 or omax >= V:
+            raise ValueError("own: index outside [-1, V)")
+    E = int(offset_vectors(q).shape[0])                    # raises over MAX_OFFSETS
+    assert E <= MAX_OFFSETS
+    return (X, own, values, pairs), (N, V, Pp, E)
+
+
 _RATE_BLOCKS = 1024      # workgroups a short partition list is spread over (4 per CU)
 _RATE_EMPTY = 0x7FFFFFFF
 
@@ -863,7 +907,7 @@ def rate_counts(be, q, lo, hi, pids, n_samples, seed, values, pairs, split: Opti
     n_samples = int(n_samples)
     if n_samples < 0 or n_samples >= _RATE_EMPTY:
         raise ValueError(f"rate: bad sample count {n_samples}")
-    if max([be.n0] + list(be.widths)) > 160 or be.n0 > 32:
+    if not _rowfwd_covers(be):
         raise ValueError("rate: the kernel covers layers up to 160 wide and up to 32 inputs")
     if split is None:
         split = _rate_split(P, n_samples)
@@ -894,33 +938,8 @@ def audit_masks(be, q, X, own, values, pairs, blocks: Optional[int] = None):
     does not cover the shape (a layer over 160 wide, over 32 inputs, more than 64 KB of LDS): the
     caller takes ``ops/audit.audit_masks_ref``.  ``blocks``: workgroups (default: one per 64-row
     pass, at most 1 024); every value gives the same outputs."""
-    from .audit import MAX_VALUES
-    from .rate import MAX_OFFSETS, offset_vectors
-
-    if X.dim() != 2 or X.shape[1] != be.n0:
-        raise ValueError(f"X: expected [N, {be.n0}], got {tuple(X.shape)}")
-    N = int(X.shape[0])
+    (X, own, values, pairs), (N, V, Pp, E) = _row_inputs(be, q, X, own, values, pairs, "audit")
     dev = X.device
-    npa = len(q.pa_idx)
-    if values.dim() != 2 or values.shape[1] != npa:
-        raise ValueError(f"values: expected [V, {npa}], got {tuple(values.shape)}")
-    V, Pp = int(values.shape[0]), int(pairs.shape[0])
-    if not 1 <= V <= MAX_VALUES:
-        raise ValueError(f"audit: {V} PA assignments, the kernel covers 1..{MAX_VALUES}")
-    X = _c(X, torch.float32, (N, be.n0), "X")
-    own = _c(own, torch.int32, (N,), "own")
-    values = _c(values, torch.int64, (V, npa), "values")
-    pairs = _c(pairs, torch.int64, (Pp, 2), "pairs")
-    if any(t.device != dev for t in (own, values, pairs, be.flat)):
-        raise ValueError("audit: X, own, values, pairs and the network must be on one device")
-    if Pp and (int(pairs.min()) < 0 or int(pairs.max()) >= V):
-        raise ValueError("pairs: index outside [0, V)")
-    if N:
-        omin, omax = torch.stack(torch.aminmax(own)).tolist()           # one read-back
-        if omin < -1 or omax >= V:
-            raise ValueError("own: index outside [-1, V)")
-    E = int(offset_vectors(q).shape[0])                    # raises over MAX_OFFSETS
-    assert E <= MAX_OFFSETS
     if blocks is None:
         blocks = min(audit_passes(N), _AUDIT_BLOCKS)
     if not 1 <= int(blocks) <= audit_passes(N):
@@ -928,13 +947,12 @@ def audit_masks(be, q, X, own, values, pairs, blocks: Optional[int] = None):
     cert = torch.zeros(N, dtype=torch.int32, device=dev)
     poss = torch.zeros(N, dtype=torch.int32, device=dev)
     sign = torch.zeros(N, dtype=torch.int8, device=dev)
-    if max([be.n0] + list(be.widths)) > 160 or be.n0 > 32:
+    if not _rowfwd_covers(be):
         return None
     if N:
         ok = ext().audit(_net(be), **_ptrs(flat=be.flat, x=X, own=own, values=values, pairs=pairs if Pp else None,
                                            cert=cert, poss=poss, own_sign=sign),
-                         N=N, V=V, pa=list(q.pa_idx), Pp=Pp, ra=list(q.ra_idx) if q.relaxed else [],
-                         tau=int(q.tau) if q.relaxed else 0, E=E, blocks=int(blocks), stream=_stream(dev))
+                         N=N, V=V, Pp=Pp, **_pairs_kw(q, E), blocks=int(blocks), stream=_stream(dev))
         if not ok:
             return None
     return cert, poss, sign
@@ -958,34 +976,10 @@ def neighbour_masks(be, q, X, own, values, pairs, table, radii=None, blocks: Opt
     ``ops/neighbours.neighbour_masks_ref``.  ``table``: an ``ops/neighbours.NeighbourTable``;
     ``radii``: [n0] per-feature radii (default: the table's).  ``blocks``: workgroups (default: one
     per work item, at most 1 024); every value gives the same outputs."""
-    from .audit import MAX_VALUES
     from .neighbours import FULL, MAX_NEIGHBOURS
-    from .rate import MAX_OFFSETS, offset_vectors
 
-    if X.dim() != 2 or X.shape[1] != be.n0:
-        raise ValueError(f"X: expected [N, {be.n0}], got {tuple(X.shape)}")
-    N = int(X.shape[0])
+    (X, own, values, pairs), (N, V, Pp, E) = _row_inputs(be, q, X, own, values, pairs, "neighbours")
     dev = X.device
-    npa = len(q.pa_idx)
-    if values.dim() != 2 or values.shape[1] != npa:
-        raise ValueError(f"values: expected [V, {npa}], got {tuple(values.shape)}")
-    V, Pp = int(values.shape[0]), int(pairs.shape[0])
-    if not 1 <= V <= MAX_VALUES:
-        raise ValueError(f"neighbours: {V} PA assignments, the kernel covers 1..{MAX_VALUES}")
-    X = _c(X, torch.float32, (N, be.n0), "X")
-    own = _c(own, torch.int32, (N,), "own")
-    values = _c(values, torch.int64, (V, npa), "values")
-    pairs = _c(pairs, torch.int64, (Pp, 2), "pairs")
-    if any(t.device != dev for t in (own, values, pairs, be.flat)):
-        raise ValueError("neighbours: X, own, values, pairs and the network must be on one device")
-    if Pp and (int(pairs.min()) < 0 or int(pairs.max()) >= V):
-        raise ValueError("pairs: index outside [0, V)")
-    if N:
-        omin, omax = torch.stack(torch.aminmax(own)).tolist()           # one read-back
-        if omin < -1 or omax >= V:
-            raise ValueError("own: index outside [-1, V)")
-    E = int(offset_vectors(q).shape[0])                    # raises over MAX_OFFSETS
-    assert E <= MAX_OFFSETS
     M, W = table.M, table.W
     if M > MAX_NEIGHBOURS:
         raise ValueError(f"neighbours: {M} table entries, at most {MAX_NEIGHBOURS}")
@@ -1002,7 +996,7 @@ def neighbour_masks(be, q, X, own, values, pairs, table, radii=None, blocks: Opt
         raise ValueError(f"neighbours: {blocks} workgroups outside 1..{neighbour_items(N, M)}")
     cert = torch.zeros(N, W, dtype=torch.int32, device=dev)
     poss = torch.zeros(N, W, dtype=torch.int32, device=dev)
-    if max([be.n0] + list(be.widths)) > 160 or be.n0 > 32:
+    if not _rowfwd_covers(be):
         return None
     if N and M:
         i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64).clip(-FULL - 1, FULL)
@@ -1011,9 +1005,7 @@ def neighbour_masks(be, q, X, own, values, pairs, table, radii=None, blocks: Opt
                     dom_hi=i32(table.hi), radius=i32(radii))
         ok = ext().neighbours(_net(be), **_ptrs(flat=be.flat, x=X, own=own, values=values,
                                                 pairs=pairs if Pp else None, cert=cert, poss=poss, **tabs),
-                              N=N, V=V, pa=list(q.pa_idx), Pp=Pp, ra=list(q.ra_idx) if q.relaxed else [],
-                              tau=int(q.tau) if q.relaxed else 0, E=E, M=M, W=W, blocks=int(blocks),
-                              stream=_stream(dev))
+                              N=N, V=V, Pp=Pp, **_pairs_kw(q, E), M=M, W=W, blocks=int(blocks), stream=_stream(dev))
         if not ok:
             return None
     return cert, poss
@@ -1067,7 +1059,7 @@ def causal_codes(be, X, table, blocks: Optional[int] = None):
     if not 1 <= int(blocks) <= causal_items(S, T):
         raise ValueError(f"causal: {blocks} workgroups outside 1..{causal_items(S, T)}")
     code = torch.zeros(S, T, dtype=torch.uint8, device=dev)
-    if max([be.n0] + list(be.widths)) > 160 or be.n0 > 32:
+    if not _rowfwd_covers(be):
         return None
     if S and T:
         order = np.argsort(-table.count.astype(np.int64), kind="stable")
@@ -1125,7 +1117,7 @@ def count_enum(be, q, lo, hi, values, pairs, max_vol: Optional[int] = None, bloc
     values = _c(values, torch.int64, None, "values")
     pairs = _c(pairs, torch.int64, (pairs.shape[0], 2), "pairs")
     V, Pp, E = _count_shape(be, q, values, pairs, "count_enum")
-    if max([be.n0] + list(be.widths)) > 160 or be.n0 > 32:
+    if not _rowfwd_covers(be):
         raise ValueError("count_enum: the kernel covers layers up to 160 wide and up to 32 inputs")
     if max_vol is None:
         max_vol = int(volumes(lo, hi, free_dims(q)).max()) if L else 1
@@ -1141,8 +1133,7 @@ def count_enum(be, q, lo, hi, values, pairs, max_vol: Optional[int] = None, bloc
     if L:
         ext().count_enum(_net(be), **_ptrs(flat=be.flat, lo=lo, hi=hi, values=values, pairs=pairs if Pp else None,
                                            cert=cert, amb=amb, amb_idx=idx),
-                         L=L, V=V, pa=list(q.pa_idx), Pp=Pp, ra=list(q.ra_idx) if q.relaxed else [],
-                         tau=int(q.tau) if q.relaxed else 0, E=E, max_vol=int(max_vol), blocks=int(blocks),
+                         L=L, V=V, Pp=Pp, **_pairs_kw(q, E), max_vol=int(max_vol), blocks=int(blocks),
                          stream=_stream(dev))
         idx = idx.masked_fill((amb > AMB_SLOTS)[:, None], _RATE_EMPTY).sort(dim=1).values
     return cert, amb, idx
@@ -1186,7 +1177,7 @@ def gap_enum(be, q, lo, hi, values, pairs, max_vol: Optional[int] = None, blocks
         blocks = min(max(L, 1), max(_ENUM_BLOCKS, L * int(max_vol) // _ENUM_POINTS))
     if L and not 1 <= int(blocks) <= L:
         raise ValueError(f"gap_enum: {blocks} workgroups outside 1..{L}")
-    if max([be.n0] + list(be.widths)) > 160 or be.n0 > 32:
+    if not _rowfwd_covers(be):
         return None
     leaf_lo = torch.zeros(L, dtype=torch.float64, device=dev)
     leaf_hi = torch.zeros(L, dtype=torch.float64, device=dev)
@@ -1194,8 +1185,7 @@ def gap_enum(be, q, lo, hi, values, pairs, max_vol: Optional[int] = None, blocks
     if L:
         ok = ext().gap_enum(_net(be), **_ptrs(flat=be.flat, lo=lo, hi=hi, values=values, pairs=pairs, leaf_lo=leaf_lo,
                                               leaf_hi=leaf_hi, arg_s=arg[0], arg_pair=arg[1], arg_e=arg[2]),
-                            L=L, V=V, pa=list(q.pa_idx), Pp=Pp, ra=list(q.ra_idx) if q.relaxed else [],
-                            tau=int(q.tau) if q.relaxed else 0, E=E, max_vol=int(max_vol), blocks=int(blocks),
+                            L=L, V=V, Pp=Pp, **_pairs_kw(q, E), max_vol=int(max_vol), blocks=int(blocks),
                             stream=_stream(dev))
         if not ok:
             return None
